@@ -21,6 +21,16 @@ annotation -> JSON report rendered -> exit code.  Nothing is cached between
 steps.  ``--mode sweep`` additionally re-probes every GPU and re-PATCHes its
 annotation inside each step.
 
+A plain run does only that: it sets up, warms up, times ``--steps`` steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given, and prints the line.  Everything below except the agent's diagnostics (part of the
+setup: they are in the annotation the timed check judges) runs only with ``--full``; a plain run's line carries
+``null`` in those places.
+
+``--dump-outputs DIR`` (rank 0, after the timed steps): what the last timed check handed its caller, as
+``DIR/<name>.npy`` -- ``report_json`` (the rendered report's UTF-8 bytes), ``exit_code``, and per GPU node ``ready``,
+``verdict_state`` (index into healthy/degraded/unhealthy/unknown, -1: no report) and ``verdict_gpus`` (ok, seen).
+The mock cluster is the same for the same arguments, so two builds can be compared file for file.
+
 Untimed extras (coldstart runs, the agent's diagnostics, the RCCL fabric check and the multi-GPU node
 cycle) share one wall-clock budget (``--extras-budget``, 180 s from start): an extra that would not fit in
 what is left is recorded as ``{"skipped": "budget"}``, the node-cycle child is killed at the budget, and the
@@ -28,8 +38,8 @@ timed loop never waits on any of them.  Every phase's wall time is in the line (
 timed step's milliseconds go -- connect, first byte, body, scan, health gate, render -- as medians
 (``step_ms``).
 
-Node-count curve (``curve``; rank 0, after the headline, others at the closing barrier): the same check, same
-``--steps`` / ``--warmup``, against one mock cluster per node count of ``--curve`` (1/2/4/8/16/1000; each server
+Node-count curve (``--full``: ``curve``; rank 0, after the headline, others at the closing barrier): the same
+check, same ``--steps`` / ``--warmup``, against one mock cluster per node count of ``--curve`` (1/2/4/8/16/1000; each server
 started with the headline's, before any GPU work, its nodes carrying the recorded MI355X probe annotation).  Every
 row -- the headline's own is one -- has ms per check, nodes/s, the survey proxy's ms at that count
 (``baseline_basis``: a different machine), ``vs_baseline``, and ``checker_ms``: the checker's own part of a check
@@ -38,7 +48,7 @@ and the mock's time).
 
 Placement (``cpu_pair``; ``--no-pin``): the mock apiservers run on one CPU and rank 0's checking thread on the
 other CPUs of that CPU's L3 domain, for the timed steps and the curve; the line's ``pinning`` says which, and
-``unpinned`` is the headline's check timed once more at the end with neither side pinned.
+``unpinned`` (``--full``) is the headline's check timed once more at the end with neither side pinned.
 
 Prints ONE JSON line (rank 0): value = nodes/s over the whole job (headline node count = GPUs).
 """
@@ -332,6 +342,38 @@ def _timed_checks(cluster, opts, steps: int, warmup: int) -> "tuple[float, list,
     return time.perf_counter() - t0, lat, spans, last
 
 
+# --dump-outputs: at most this many bytes in all; a larger array is cut to a fixed, seeded sample of its elements
+DUMP_LIMIT_BYTES = 64 << 20
+VERDICT_STATES = ("healthy", "degraded", "unhealthy", "unknown")
+
+
+def dump_outputs(path: str, last, report_text: str) -> dict:
+    """Write what the last timed check handed its caller as ``path/<name>.npy`` (float32 / float64):
+    {name: shape}.  The arrays share DUMP_LIMIT_BYTES in proportion to their sizes."""
+    import numpy as np
+    nodes = last.gpu_nodes
+    verdicts = list(last.verdicts or []) + [None] * len(nodes)
+    arrays = {
+        "report_json": np.frombuffer(report_text.encode("utf-8"), dtype=np.uint8).astype(np.float32),
+        "exit_code": np.array([last.exit_code], dtype=np.float64),
+        "ready": np.array([1.0 if n.get("ready") else 0.0 for n in nodes], dtype=np.float64),
+        "verdict_state": np.array([VERDICT_STATES.index(v.state) if v is not None else -1
+                                   for v in verdicts[:len(nodes)]], dtype=np.float64),
+        "verdict_gpus": np.array([(v.gpus_ok, v.gpus_seen) if v is not None else (-1, -1)
+                                  for v in verdicts[:len(nodes)]], dtype=np.float64).reshape(len(nodes), 2),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * DUMP_LIMIT_BYTES / total) - 1)
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def curve_row(nodes: int, elapsed: float, steps: int, lat: list, spans: list, last, slack: bool,
               annotations: str) -> dict:
     """One point of the node-count curve: the same numbers as the headline (ms per check, nodes/s, the
@@ -358,15 +400,22 @@ def main() -> int:
     ap.add_argument("--diag-level", type=int, default=1, choices=(0, 1, 2))
     ap.add_argument("--slack", action="store_true", help="also POST the Slack report to a local sink each step")
     ap.add_argument("--page-size", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: coldstart runs, the node-count curve, the unpinned "
+                         "re-run, and with more than one rank the fabric check and the multi-GPU node cycle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed check returned (report bytes, exit code, "
+                         "per-node ready flags and health verdicts) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--curve", default=CURVE_NODES, metavar="N,N,...",
-                    help="also time the same check (same --steps / --warmup, rank 0, after the headline) against one "
-                         f"mock cluster per node count (default {CURVE_NODES}; '' to skip); the headline's own node "
+                    help="with --full: also time the same check (same --steps / --warmup, rank 0, after the headline) "
+                         f"against one mock cluster per node count (default {CURVE_NODES}; '' to skip); the headline's own node "
                          "count is its row")
     ap.add_argument("--no-pin", dest="pin", action="store_false",
                     help="leave the checking thread and the mock apiservers where the scheduler puts them (default: two "
                          "CPUs of one L3 domain, cpu_pair())")
     ap.add_argument("--coldstart-runs", type=int, default=11,
-                    help="child-process runs of check-gpu-node --json for coldstart_ms (rank 0, before GPU work; 0: skip)")
+                    help="with --full: child-process runs of check-gpu-node --json for coldstart_ms (rank 0, before GPU "
+                         "work; 0: skip)")
     ap.add_argument("--no-fabric-check", dest="fabric_check", action="store_false",
                     help="skip the untimed all-reduce fabric check (world > 1)")
     ap.add_argument("--no-node-cycle", dest="node_cycle", action="store_false",
@@ -407,13 +456,13 @@ def main() -> int:
             procs.append(p)
             ctrl["slack"] = sinfo["url"] + "/200"
         sizes = sorted({int(x) for x in args.curve.split(",") if x.strip()} - {n_nodes})
-        if sizes:
+        if sizes and args.full:
             try:
                 ctrl["curve_api"] = _curve_servers(sizes, procs, pin)
             except Exception as e:  # the curve is an extra: its servers failing must not cost the headline
                 ctrl["curve_error"] = f"{type(e).__name__}: {e}"[:300]
     budget.mark("control_plane", t_control)
-    if rank == 0 and args.coldstart_runs > 0:
+    if rank == 0 and args.full and args.coldstart_runs > 0:
         if budget.fits(COLDSTART_MIN_S):
             with budget.phase("coldstart"):
                 ctrl["coldstart"] = _coldstart(ctrl["api"], args.coldstart_runs)
@@ -516,14 +565,14 @@ def _run(args, world, rank, local_rank, n_gpus, n_nodes, ctrl, budget) -> int:
     if skipped.get("agent_diag"):
         diag = {"skipped": "budget"}
     fabric = None
-    if world > 1 and args.fabric_check:
+    if world > 1 and args.full and args.fabric_check:
         if agree(budget.fits(FABRIC_MIN_S)):
             with budget.phase("fabric"):
                 fabric = _fabric_check(world, local_rank, cuda)
         else:
             fabric = {"skipped": "budget"}
     node_cycle = None
-    if world > 1 and args.node_cycle and (cuda or args.node_cycle_always):
+    if world > 1 and args.full and args.node_cycle and (cuda or args.node_cycle_always):
         if agree(budget.fits(NODE_CYCLE_MIN_S)):
             dist.barrier(group=group)  # CPU barrier: every rank's own setup is done, its GPU idle
             with budget.phase("node_cycle"):
@@ -590,8 +639,12 @@ def _run(args, world, rank, local_rank, n_gpus, n_nodes, ctrl, budget) -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)  # the slowest rank's clock (gloo, CPU tensor)
         elapsed = float(t.item())
 
+    dumped = None
+    if rank == 0 and args.dump_outputs and last is not None:
+        dumped = dump_outputs(args.dump_outputs, last, sink_out.getvalue())
+
     curve = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the BASELINE metric's node-count axis (the reference's one LIST + per-node loop,
         # check-gpu-node.py:215-226): the headline's row, then one mock cluster per other node count, each timed
         # like the headline; the other ranks wait at the closing gloo barrier meanwhile
@@ -610,6 +663,7 @@ def _run(args, world, rank, local_rank, n_gpus, n_nodes, ctrl, budget) -> int:
     unpinned = None
     if mask is not None:
         os.sched_setaffinity(0, mask)
+    if args.full and mask is not None:
         # the headline once more with neither side pinned (the server's new request threads inherit its main
         # thread's mask): how much of the number is placement, measured in every run rather than asserted
         try:
@@ -636,6 +690,7 @@ def _run(args, world, rank, local_rank, n_gpus, n_nodes, ctrl, budget) -> int:
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -673,6 +728,7 @@ def _run(args, world, rank, local_rank, n_gpus, n_nodes, ctrl, budget) -> int:
             "probe": {"source": probe_source, "setup_ms": round(probe_ms, 1), "diag": diag},
             "fabric": fabric,
             "node_cycle": node_cycle,
+            "dumped_outputs": dumped,
             "phases_s": budget.phases,
             "extras_budget_s": {"budget": budget.total,
                                 "used": round(sum(v for k, v in budget.phases.items()

@@ -1,7 +1,7 @@
 """One node-level agent cycle over several local GPUs, as a standalone process: the multi-device paths of the
 node agent on real hardware.
 
-``bench.py`` runs it (untimed, rank 0, in a child process with a time limit) whenever it has more than one
+``bench.py --full`` runs it (untimed, rank 0, in a child process with a time limit) whenever it has more than one
 GPU: the agent's per-device diagnostic threads on every GPU at once (``--diag-parallel``, the thread-local GEMM
 knobs, the per-device dynamic-LDS attribute, the host-link lock), then the node-level xGMI pair matrix and the
 in-process RCCL suite under its deadline.  Prints one JSON line.

@@ -34,8 +34,8 @@ def last_json(out):
 
 
 def test_bench_single_process_contract():
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "30", "--warmup", "3"],
-                       capture_output=True, text=True, timeout=300, env=env(), cwd=REPO)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "30", "--warmup", "3",
+                        "--full"], capture_output=True, text=True, timeout=300, env=env(), cwd=REPO)
     assert p.returncode == 0, p.stderr
     d = last_json(p.stdout)
     assert KEYS <= set(d)
@@ -66,6 +66,36 @@ def test_bench_single_process_contract():
     assert d["unpinned"] is None if "skipped" in pin else d["unpinned"]["ms_per_step"] > 0
 
 
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full: the headline only (no coldstart, curve or unpinned re-run), and --dump-outputs writes what
+    the last timed check returned, the same from run to run."""
+    import numpy as np
+
+    def run(out):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup",
+                            "2", "--nodes", "3", "--dump-outputs", str(out)], capture_output=True, text=True,
+                           timeout=300, env=env(), cwd=REPO)
+        assert p.returncode == 0, p.stderr
+        return last_json(p.stdout)
+    d = run(tmp_path / "a")
+    assert KEYS <= set(d) and d["full"] is False and d["steps"] == 7 and d["latency_ms"]["samples"] == 7
+    assert d["check_ok"] and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(3 * 1e3 / d["ms_per_step"], rel=0.01)
+    assert d["curve"] is None and d["coldstart"] is None and d["coldstart_ms"] is None and d["unpinned"] is None
+    assert set(d["phases_s"]) == {"control_plane", "init", "agent_cycle", "publish", "warmup", "timed"}
+    names = {"report_json", "exit_code", "ready", "verdict_state", "verdict_gpus"}
+    assert set(d["dumped_outputs"]) == names == {f[:-4] for f in os.listdir(tmp_path / "a")}
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    report = json.loads(bytes(a["report_json"].astype(np.uint8)).decode("utf-8"))
+    assert report["total_nodes"] == 3 and report["ready_nodes"] == 3 and len(report["nodes"]) == 3
+    assert a["exit_code"].tolist() == [0.0] and a["ready"].tolist() == [1.0] * 3
+    assert a["verdict_state"].tolist() == [0.0] * 3 and a["verdict_gpus"].tolist() == [[1.0, 1.0]] * 3
+    run(tmp_path / "b")
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+
+
 def test_cpu_pair_and_cpu_lists():
     import bench
     assert bench._cpu_list("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11} and bench._cpu_list("5") == {5}
@@ -79,7 +109,7 @@ def test_cpu_pair_and_cpu_lists():
 def test_bench_torchrun_two_ranks_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2",
-           "--steps", "20", "--warmup", "2"]
+           "--steps", "20", "--warmup", "2", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env(), cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     d = last_json(p.stdout)
@@ -128,7 +158,7 @@ def test_collective_verdict_logic():
 def _torchrun(n, *extra, timeout=300):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", str(n),
-           "--steps", "20", "--warmup", "2", "--coldstart-runs", "2", *extra]
+           "--steps", "20", "--warmup", "2", "--full", "--coldstart-runs", "2", *extra]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env(), cwd=REPO)
 
 

@@ -600,7 +600,7 @@ def test_smoke(dev):
 
 
 def test_bench_contract_on_gpu(repo):
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "50", "--warmup", "5"],
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "50", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=repo)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")][-1]

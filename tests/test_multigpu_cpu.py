@@ -104,7 +104,7 @@ def test_bench_torchrun_four_ranks_gloo():
     from test_bench_distributed import env, free_port, last_json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "4",
-           "--steps", "20", "--warmup", "2"]
+           "--steps", "20", "--warmup", "2", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env(), cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     d = last_json(p.stdout)

@@ -504,7 +504,9 @@ def test_slack_url_credentials_identical(cluster, sink, tmp_path):
     assert ("Authorization", "Basic bnU6bnA=") in rb[0][2]
 
 
-@pytest.mark.parametrize("url,env", [("http://127.0.0.1:99999/x", None), ("http://[::1/x", None),
+# "::" separates the parts of a pytest node id: the IPv6 case gets an id that can be selected by name
+@pytest.mark.parametrize("url,env", [("http://127.0.0.1:99999/x", None),
+                                     pytest.param("http://[::1/x", None, id="http://[:_:1/x-None"),
                                      ("https://127.0.0.1:1/x", {"REQUESTS_CA_BUNDLE": "/missing"}),
                                      ("http://127.0.0.1:1/x", None), ("ftp://x/y", None)])
 @pytest.mark.parametrize("flags", [[], ["--json"]])

@@ -23,7 +23,12 @@ def _ours(u):
     return urls.split(u).astuple()
 
 
-@pytest.mark.parametrize("u", CASES)
+def _case(u):
+    # "::" separates the parts of a pytest node id: a case that holds it gets an id that can be selected by name
+    return pytest.param(u, id=u.replace("::", ":_:")) if "::" in u else u
+
+
+@pytest.mark.parametrize("u", [_case(u) for u in CASES])
 def test_split_matches_urlsplit(u):
     try:
         ref = _ref(u)

@@ -58,7 +58,9 @@ def test_url_credentials(sink, userinfo, path, monkeypatch):
         assert ("Authorization", "Basic dTpw") in b[1][0][2]
 
 
-@pytest.mark.parametrize("url", ["http://127.0.0.1:99999/x", "http://[::1/x", "http://[::1]:70000/x", "ftp://x/y",
+# "::" separates the parts of a pytest node id: the IPv6 cases get ids that can be selected by name
+@pytest.mark.parametrize("url", ["http://127.0.0.1:99999/x", pytest.param("http://[::1/x", id="http://[:_:1/x"),
+                                 pytest.param("http://[::1]:70000/x", id="http://[:_:1]:70000/x"), "ftp://x/y",
                                  "nohost", "http://", "  http://127.0.0.1:1/x", "http://no-such-host.invalid/x",
                                  "http://.bad/x", "http://127.0.0.1:1/x"])
 def test_url_and_connection_errors(sink, url, monkeypatch):
