@@ -1598,6 +1598,17 @@ __global__ void __launch_bounds__(256) write_kernel(f32x4* __restrict__ dst, siz
   if (i < n) dst[i] = f32x4{v, v, v, v};
 }
 
+// The bytes the stream rates are computed from, checked outside the timed loops: every 16-byte element of `p` must
+// hold `v` in all four lanes; one atomic per wrong element, as mt_verify_kernel.
+__global__ void __launch_bounds__(256) stream_verify_kernel(const f32x4* __restrict__ p, size_t n, float v,
+                                                            unsigned long long* errors) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+    const f32x4 x = p[i];
+    if (x[0] != v || x[1] != v || x[2] != v || x[3] != v) atomicAdd(errors, 1ULL);
+  }
+}
+
 // one thread per 16-byte element (grid-stride kernels launched with it run their loop once)
 unsigned flat_grid(size_t n) { return static_cast<unsigned>(std::min<size_t>((n + 255) / 256, 0x7FFFFFFFu)); }
 
@@ -1634,6 +1645,22 @@ __global__ void __launch_bounds__(256) mt_verify_kernel(const uint4* p, size_t n
       atomicMin(first_bad, static_cast<unsigned long long>(i));
     }
   }
+}
+
+// Self-check hook of the per-XCD readers: one bit of 32-bit word `word` of XCD `xcd`'s slice is flipped from the host
+// (after the fill, before the first launch).  Returns -2 with g_err set when the word lies outside the slice.
+int flip_slice_word(void* buf, uint32_t slice_vec, int xcd, long long word, const char* what) {
+  if (xcd < 0) return 0;
+  if (xcd > 7 || word < 0 || word >= 4LL * slice_vec) {
+    g_err = std::string(what) + ": inject_xcd 0..7 and inject_word inside the slice";
+    return -2;
+  }
+  uint32_t* w = static_cast<uint32_t*>(buf) + 4ULL * slice_vec * static_cast<unsigned>(xcd) + word;
+  uint32_t v = 0;
+  DIAG_CHECK(hipMemcpy(&v, w, sizeof v, hipMemcpyDeviceToHost));
+  v ^= 0x10u;
+  DIAG_CHECK(hipMemcpy(w, &v, sizeof v, hipMemcpyHostToDevice));
+  return 0;
 }
 
 int grid_for(int device, int blocks_per_cu) {
@@ -1700,7 +1727,7 @@ __device__ __forceinline__ unsigned wave_slot() {
 
 template <int KIND>
 __global__ void __launch_bounds__(256) mfma_burn_kernel(const i32x8* __restrict__ fa, const i32x8* __restrict__ fb,
-                                                        const float* __restrict__ expect, int iters,
+                                                        const float* __restrict__ expect, int iters, int inject_block,
                                                         unsigned long long* errors, unsigned long long* cu_map) {
   const long long t0 = wall_clock64();  // constant-rate clock (hipDeviceAttributeWallClockRate)
   const int lane = threadIdx.x & 63;
@@ -1716,7 +1743,11 @@ __global__ void __launch_bounds__(256) mfma_burn_kernel(const i32x8* __restrict_
     }
   }
   const floatx4 s = acc0 + acc1 + acc2 + acc3;
-  const bool bad = s[0] + s[1] + s[2] + s[3] != expect[lane];
+  float sum = s[0] + s[1] + s[2] + s[3];
+  // the self-check of the verifier (diag_mfma_burn_map_x): one lane of one workgroup is made wrong by one, which
+  // is exact below 2^24 and so always differs
+  if (static_cast<int>(blockIdx.x) == inject_block && threadIdx.x == 0) sum += 1.0f;
+  const bool bad = sum != expect[lane];
   if (bad) atomicAdd(errors, 1ULL);
   if (cu_map != nullptr) {
     // per physical CU: waves run, wrong lanes, summed wave time -- a miscomputing CU is named, and an
@@ -2115,13 +2146,15 @@ std::vector<int> tile_xcds(int tiles_m, int tiles_n, int group_m) {
 
 // Whole-output check of C = A . Bt^T (the ck_* kernels).  ck_out[0] bad tiles, [1] bad columns, [2..9] bad tiles
 // per XCD, [10] / [11] the first bad tile's (row, column) in tiles or -1; *max_err the worst |csum - ref| / mag.
-// A NaN or infinite sum counts as bad.
+// A NaN or infinite sum counts as bad.  *floor_out (optional) = tol * the largest mag of any column: an output wrong
+// by more than that (plus the healthy residual) is flagged whichever column it is in.
 constexpr int kCkOut = 12;
 // With `fused` (the OUT_BF16_CK kernel's csum[M / 128][N], device memory) the column sums come from the
 // kernel itself, its 128-row halves added per tile row in fp64, and C is not read.
 template <int DT>
 int gemm_checksum(int device, const void* A, const void* Bt, const float* C, int M, int N, int K, TileGeom g,
-                  double tol, double* max_err, long long* ck_out, const double* fused = nullptr) {
+                  double tol, double* max_err, long long* ck_out, const double* fused = nullptr,
+                  double* floor_out = nullptr) {
   const int rb = g.rows;
   const int nblk = M / rb, tiles_n = N / g.cols;
   const size_t kb = sizeof(double) * static_cast<size_t>(nblk) * K, nb = sizeof(double) * static_cast<size_t>(nblk) * N;
@@ -2159,9 +2192,10 @@ int gemm_checksum(int device, const void* A, const void* Bt, const float* C, int
   }
   const std::vector<int> xcd = tile_xcds(nblk, tiles_n, g.group_m);
   std::vector<char> bad(static_cast<size_t>(nblk) * tiles_n, 0);
-  double worst = 0.0;
+  double worst = 0.0, max_mag = 0.0;
   long long cols = 0;
   for (size_t i = 0; i < cnt; ++i) {
+    max_mag = std::max(max_mag, hm[i]);
     const double e = std::fabs(hc[i] - hr[i]) / std::max(hm[i], 1e-30);
     if (!(e <= tol)) {  // also NaN
       ++cols;
@@ -2183,29 +2217,39 @@ int gemm_checksum(int device, const void* A, const void* Bt, const float* C, int
     }
   }
   *max_err = worst;
+  if (floor_out != nullptr) *floor_out = tol * max_mag;
   return 0;
 }
 
-// A test hook: overwrite output element `elem` of C with 1e6 (an error every check must see).
-hipError_t inject_output(float* C, long long elem, long long count) {
+// A test hook: overwrite output element `elem` of C with 1e6 (an error every check must see) or, with a `delta`
+// that is not NaN, with its own value plus delta (the smallest error the checksums must see).
+hipError_t inject_output(float* C, long long elem, long long count, double delta) {
   if (elem < 0 || elem >= count) return hipSuccess;
-  const float v = 1e6f;
+  float v = 1e6f;
+  if (!std::isnan(delta)) {
+    float old;
+    const hipError_t e = hipMemcpy(&old, C + elem, sizeof(old), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    v = static_cast<float>(static_cast<double>(old) + delta);
+  }
   return hipMemcpy(C + elem, &v, sizeof(v), hipMemcpyHostToDevice);
 }
 
 // The same for the bf16-output kernel: the element becomes 1e6 in C and in its 128-row block's fused column
-// sum, as if the matrix core had produced that value.
-hipError_t inject_output_ck(__bf16* C, double* csum, long long elem, int M, int N) {
+// sum, as if the matrix core had produced that value.  With `delta` the fused sum (formed from the fp32
+// accumulators, before the rounding) moves by exactly delta and C holds the rounded old + delta.
+hipError_t inject_output_ck(__bf16* C, double* csum, long long elem, int M, int N, double delta) {
   if (elem < 0 || elem >= static_cast<long long>(M) * N) return hipSuccess;
   __bf16 old;
   hipError_t e = hipMemcpy(&old, C + elem, sizeof(old), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return e;
-  const __bf16 v = static_cast<__bf16>(1e6f);
+  const bool by_delta = !std::isnan(delta);
+  const __bf16 v = static_cast<__bf16>(by_delta ? static_cast<float>(static_cast<float>(old) + delta) : 1e6f);
   if ((e = hipMemcpy(C + elem, &v, sizeof(v), hipMemcpyHostToDevice)) != hipSuccess) return e;
   double* cs = csum + (elem / N) / 128 * N + elem % N;
   double sum;
   if ((e = hipMemcpy(&sum, cs, sizeof(sum), hipMemcpyDeviceToHost)) != hipSuccess) return e;
-  sum += static_cast<double>(static_cast<float>(v)) - static_cast<double>(static_cast<float>(old));
+  sum += by_delta ? delta : static_cast<double>(static_cast<float>(v)) - static_cast<double>(static_cast<float>(old));
   return hipMemcpy(cs, &sum, sizeof(sum), hipMemcpyHostToDevice);
 }
 
@@ -2385,10 +2429,11 @@ int diag_gemm_ck_path(int dt, int M, int N) {
 
 // Self-contained MFMA burn-in: allocate, fill, run `iters` GEMMs, time them, verify `nsamp` sampled outputs
 // against the fp32 reference kernel and, with ck_tol >= 0, every output by tile checksums (gemm_checksum:
-// *ck_err, ck_out[kCkOut]).  `inject_elem` >= 0 overwrites that output between the timing and the checks.
-int diag_gemm_bf16_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                     double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter, double* ck_err,
-                     long long* ck_out) {
+// *ck_err, ck_out[kCkOut], *ck_floor).  `inject_elem` >= 0 overwrites that output between the timing and the
+// checks: with 1e6, or (inject_delta not NaN) with its own value plus inject_delta.
+int diag_gemm_bf16_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                      double inject_delta, double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter,
+                      double* ck_err, long long* ck_out, double* ck_floor) {
   if (inject_elem >= static_cast<long long>(M) * N) {
     g_err = "gemm: inject_elem outside the output";
     return -2;
@@ -2447,8 +2492,8 @@ int diag_gemm_bf16_x(int device, int M, int N, int K, int warmup, int iters, int
   float t_ms = 0.f;
   DIAG_CHECK(event_ms(e0, e1, &t_ms));
   const double ms = t_ms / std::max(iters, 1);
-  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(bC.ptr), cs, inject_elem, M, N));
-  else DIAG_CHECK(inject_output(C, inject_elem, static_cast<long long>(M) * N));
+  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(bC.ptr), cs, inject_elem, M, N, inject_delta));
+  else DIAG_CHECK(inject_output(C, inject_elem, static_cast<long long>(M) * N, inject_delta));
   hipLaunchKernelGGL(gemm_ref_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, A, Bt, rows, cols, ref,
                      nsamp, K);
   DIAG_CHECK(hipGetLastError());
@@ -2476,9 +2521,17 @@ int diag_gemm_bf16_x(int device, int M, int N, int K, int warmup, int iters, int
   if (ck_tol >= 0.0) {
     const int v = bf16_variant(M, N);
     return gemm_checksum<DT_BF16>(device, A, Bt, C, M, N, K, v == 1 ? kGeomV1 : kGeomV3, ck_tol, ck_err, ck_out,
-                                  fused ? cs : nullptr);
+                                  fused ? cs : nullptr, ck_floor);
   }
   return 0;
+}
+
+// The entry point without the delta hook and the floor (the 1e6 overwrite)
+int diag_gemm_bf16_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                     double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter, double* ck_err,
+                     long long* ck_out) {
+  return diag_gemm_bf16_x2(device, M, N, K, warmup, iters, nsamp, inject_elem, std::nan(""), ck_tol, tflops,
+                           max_rel_err, ms_per_iter, ck_err, ck_out, nullptr);
 }
 
 int diag_gemm_bf16(int device, int M, int N, int K, int warmup, int iters, int nsamp, double* tflops,
@@ -2488,9 +2541,9 @@ int diag_gemm_bf16(int device, int M, int N, int K, int warmup, int iters, int n
 }
 
 // MX-fp8 counterpart of diag_gemm_bf16_x: *max_err = max |C - ref| / sum|a*b| over the samples.
-int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                    double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
-                    long long* ck_out) {
+int diag_gemm_fp8_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                      double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter,
+                      double* ck_err, long long* ck_out, double* ck_floor) {
   if (inject_elem >= static_cast<long long>(M) * N) {
     g_err = "gemm: inject_elem outside the output";
     return -2;
@@ -2546,8 +2599,8 @@ int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int 
   float t_ms = 0.f;
   DIAG_CHECK(event_ms(e0, e1, &t_ms));
   const double ms = t_ms / std::max(iters, 1);
-  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(C.ptr), cs, inject_elem, M, N));
-  else DIAG_CHECK(inject_output(c, inject_elem, static_cast<long long>(M) * N));
+  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(C.ptr), cs, inject_elem, M, N, inject_delta));
+  else DIAG_CHECK(inject_output(c, inject_elem, static_cast<long long>(M) * N, inject_delta));
   const int* r = static_cast<const int*>(rows.ptr);
   const int* cl = static_cast<const int*>(cols.ptr);
   hipLaunchKernelGGL(gemm_ref_fp8_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
@@ -2575,8 +2628,15 @@ int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int 
   *tflops = 2.0 * M * N * static_cast<double>(K) / (ms * 1e-3) / 1e12;
   if (ck_tol >= 0.0)
     return gemm_checksum<DT_FP8>(device, A.ptr, Bt.ptr, c, M, N, K, kGeomV3, ck_tol, ck_err, ck_out,
-                                 fused ? cs : nullptr);
+                                 fused ? cs : nullptr, ck_floor);
   return 0;
+}
+
+int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                    double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
+                    long long* ck_out) {
+  return diag_gemm_fp8_x2(device, M, N, K, warmup, iters, nsamp, inject_elem, std::nan(""), ck_tol, tflops, max_err,
+                          ms_per_iter, ck_err, ck_out, nullptr);
 }
 
 int diag_gemm_fp8(int device, int M, int N, int K, int warmup, int iters, int nsamp, double* tflops,
@@ -2585,11 +2645,33 @@ int diag_gemm_fp8(int device, int M, int N, int K, int warmup, int iters, int ns
                          nullptr);
 }
 
-// HBM streams over `bytes` per buffer: copy (read+write), read-only, write-only, in TB/s.
-int diag_hbm_bandwidth(int device, size_t bytes, int iters, double* copy_tbs, double* read_tbs, double* write_tbs) {
+// HBM streams over `bytes` per buffer: copy (read+write), read-only, write-only, in TB/s.  The bytes the rates are
+// computed from are checked outside the timed loops (stream_verify_kernel): after the copy phase every 16-byte
+// element of the destination holds the source's fill, after the write phase the written value; *errors = elements
+// that did not.  `inject_word` >= 0 (the verifier's self-check) overwrites that element of the destination from the
+// host before the verification of `inject_phase` (0 = the copy's, 1 = the write's).
+int diag_hbm_bandwidth_x(int device, size_t bytes, int iters, long long inject_word, int inject_phase,
+                         double* copy_tbs, double* read_tbs, double* write_tbs, unsigned long long* errors) {
   DIAG_CHECK(hipSetDevice(device));
   const size_t n = bytes / sizeof(f32x4);
-  DevBuf ba, bb, bsink;
+  if (inject_word >= 0 && (static_cast<size_t>(inject_word) >= n || inject_phase < 0 || inject_phase > 1)) {
+    g_err = "hbm: inject_word outside the buffer (or inject_phase not 0 / 1)";
+    return -2;
+  }
+  DevBuf ba, bb, bsink, berr;
+  DIAG_CHECK(berr.alloc(device, sizeof(unsigned long long)));
+  DIAG_CHECK(hipMemset(berr.ptr, 0, sizeof(unsigned long long)));
+  auto verify = [&](int phase, float want) -> int {
+    f32x4* dst = static_cast<f32x4*>(bb.ptr);
+    if (inject_word >= 0 && phase == inject_phase) {
+      const float bad[4] = {want, -want, want, want};  // one lane of the element wrong
+      DIAG_CHECK(hipMemcpy(dst + inject_word, bad, sizeof bad, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(stream_verify_kernel, dim3(flat_grid(n)), dim3(256), 0, nullptr, dst, n, want,
+                       static_cast<unsigned long long*>(berr.ptr));
+    DIAG_CHECK(hipGetLastError());
+    return 0;
+  };
   DIAG_CHECK(ba.alloc(device, n * sizeof(f32x4)));
   DIAG_CHECK(bb.alloc(device, n * sizeof(f32x4)));
   DIAG_CHECK(bsink.alloc(device, sizeof(float)));
@@ -2621,6 +2703,7 @@ int diag_hbm_bandwidth(int device, size_t bytes, int iters, double* copy_tbs, do
   DIAG_CHECK(hipEventSynchronize(e1));
   DIAG_CHECK(event_ms(e0, e1, &t_ms));
   *read_tbs = 1.0 * nb * iters / (t_ms * 1e-3) / 1e12;
+  if (verify(0, 1.0f)) return -1;  // b is still the copy of a (the read phase only reads a)
   // write
   hipLaunchKernelGGL(write_kernel, dim3(grid), dim3(256), 0, nullptr, b, n, 3.0f);
   DIAG_CHECK(hipEventRecord(e0, nullptr));
@@ -2629,18 +2712,32 @@ int diag_hbm_bandwidth(int device, size_t bytes, int iters, double* copy_tbs, do
   DIAG_CHECK(hipEventSynchronize(e1));
   DIAG_CHECK(event_ms(e0, e1, &t_ms));
   *write_tbs = 1.0 * nb * iters / (t_ms * 1e-3) / 1e12;
+  if (verify(1, 3.0f)) return -1;
   DIAG_CHECK(hipGetLastError());
+  DIAG_CHECK(hipMemcpy(errors, berr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
 }
 
+int diag_hbm_bandwidth(int device, size_t bytes, int iters, double* copy_tbs, double* read_tbs, double* write_tbs) {
+  unsigned long long errors = 0;
+  return diag_hbm_bandwidth_x(device, bytes, iters, -1, 0, copy_tbs, read_tbs, write_tbs, &errors);
+}
+
 // Pattern test over `bytes` of HBM; `passes` x (pattern, inverted pattern).
-// `inject_word` >= 0: that 16-byte word is overwritten (0xA5 bytes) between the first write and its verify --
-// the fault-injection check that a corrupted word is counted and located (diag.memtest(inject_word=...))
-int diag_memtest_x(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
-                   unsigned long long* errors, unsigned long long* first_bad_byte, double* gbps) {
+// `inject_word` >= 0: that 16-byte word is overwritten (0xA5 bytes) between one write and its verify -- the write
+// of pass `inject_pass`, its inverted half when `inject_invert` -- the fault-injection check that a corrupted word
+// is counted and located (diag.memtest(inject_word=...)); `inject_word2` >= 0 is a second word of the same write.
+int diag_memtest_x2(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
+                    long long inject_word2, int inject_pass, int inject_invert, unsigned long long* errors,
+                    unsigned long long* first_bad_byte, double* gbps) {
   DIAG_CHECK(hipSetDevice(device));
-  if (inject_word >= 0 && static_cast<size_t>(inject_word) >= bytes / sizeof(uint4)) {
-    g_err = "memtest: inject_word outside the buffer";
+  for (const long long w : {inject_word, inject_word2})
+    if (w >= 0 && static_cast<size_t>(w) >= bytes / sizeof(uint4)) {
+      g_err = "memtest: inject_word outside the buffer";
+      return -2;
+    }
+  if ((inject_word >= 0 || inject_word2 >= 0) && (inject_pass < 0 || inject_pass >= passes)) {
+    g_err = "memtest: inject_pass outside the passes";
     return -2;
   }
   const size_t n = bytes / sizeof(uint4);
@@ -2660,8 +2757,9 @@ int diag_memtest_x(int device, size_t bytes, uint64_t seed, int passes, long lon
     for (int inv = 0; inv < 2; ++inv) {
       const uint64_t s = seed + static_cast<uint64_t>(pass) * 0x9E3779B97F4A7C15ULL;
       hipLaunchKernelGGL(mt_write_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv);
-      if (inject_word >= 0 && pass == 0 && inv == 0)
-        DIAG_CHECK(hipMemsetAsync(p + inject_word, 0xA5, sizeof(uint4), nullptr));
+      if (pass == inject_pass && inv == (inject_invert ? 1 : 0))
+        for (const long long w : {inject_word, inject_word2})
+          if (w >= 0) DIAG_CHECK(hipMemsetAsync(p + w, 0xA5, sizeof(uint4), nullptr));
       hipLaunchKernelGGL(mt_verify_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv, dev, dev + 1);
     }
   }
@@ -2676,6 +2774,11 @@ int diag_memtest_x(int device, size_t bytes, uint64_t seed, int passes, long lon
   DIAG_CHECK(event_ms(e0, e1, &t_ms));
   *gbps = 4.0 * passes * static_cast<double>(n * sizeof(uint4)) / (t_ms * 1e-3) / 1e9;
   return 0;
+}
+
+int diag_memtest_x(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
+                   unsigned long long* errors, unsigned long long* first_bad_byte, double* gbps) {
+  return diag_memtest_x2(device, bytes, seed, passes, inject_word, -1, 0, 0, errors, first_bad_byte, gbps);
 }
 
 int diag_memtest(int device, size_t bytes, uint64_t seed, int passes, unsigned long long* errors,
@@ -2958,6 +3061,8 @@ int diag_p2p_fan_t(int src, const int* dsts, int ndst, size_t bytes, int iters, 
 // iterations on every CU; *tflops = dense rate, *errors = wave-lanes whose exact result differed.
 int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
                        unsigned long long* cu_map);
+int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* tflops,
+                         unsigned long long* errors, unsigned long long* cu_map);
 
 int diag_mfma_burn(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors) {
   return diag_mfma_burn_map(device, kind, iters, reps, tflops, errors, nullptr);
@@ -2969,6 +3074,13 @@ int diag_mfma_burn_slots(void) { return BURN_SLOTS; }
 // wall-clock ticks) per physical CU slot (wave_slot()), over every launch including the warm-up.
 int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
                        unsigned long long* cu_map) {
+  return diag_mfma_burn_map_x(device, kind, iters, reps, -1, tflops, errors, cu_map);
+}
+
+// `inject_block` >= 0 (the verifier's self-check): in the warm-up launch only -- it is checked and mapped like the
+// others, and a block index lands on another CU in every launch -- lane 0 of wave 0 of that workgroup is made wrong.
+int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* tflops,
+                         unsigned long long* errors, unsigned long long* cu_map) {
   if (kind < 0 || kind > 3 || iters < 1 || iters > 65536 || reps < 1) {
     g_err = "mfma_burn: kind 0..3, 1 <= iters <= 65536, reps >= 1";
     return -2;
@@ -3041,27 +3153,31 @@ int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops
   DIAG_CHECK(hipMemcpy(dex.ptr, expect.data(), expect.size() * sizeof(float), hipMemcpyHostToDevice));
   DIAG_CHECK(hipMemset(dcnt.ptr, 0, sizeof(unsigned long long)));
   const int blocks = grid_for(device, 2);  // 8 waves per CU = 2 per SIMD
-  auto launch = [&]() {
+  if (inject_block >= blocks) {
+    g_err = "mfma_burn: inject_block outside the grid";
+    return -2;
+  }
+  auto launch = [&](int inj) {
     const i32x8* a = static_cast<const i32x8*>(dfa.ptr);
     const i32x8* b = static_cast<const i32x8*>(dfb.ptr);
     const float* ex = static_cast<const float*>(dex.ptr);
     unsigned long long* c = static_cast<unsigned long long*>(dcnt.ptr);
     unsigned long long* m = static_cast<unsigned long long*>(dmap.ptr);  // null without a map
     switch (kind) {
-      case 0: hipLaunchKernelGGL(mfma_burn_kernel<0>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, c, m); break;
-      case 1: hipLaunchKernelGGL(mfma_burn_kernel<1>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, c, m); break;
-      case 2: hipLaunchKernelGGL(mfma_burn_kernel<2>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, c, m); break;
-      default: hipLaunchKernelGGL(mfma_burn_kernel<3>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, c, m);
+      case 0: hipLaunchKernelGGL(mfma_burn_kernel<0>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m); break;
+      case 1: hipLaunchKernelGGL(mfma_burn_kernel<1>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m); break;
+      case 2: hipLaunchKernelGGL(mfma_burn_kernel<2>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m); break;
+      default: hipLaunchKernelGGL(mfma_burn_kernel<3>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m);
     }
   };
-  launch();  // warm-up (also checked)
+  launch(inject_block < 0 ? -1 : inject_block);  // warm-up (also checked)
   DIAG_CHECK(hipGetLastError());
   DIAG_CHECK(hipDeviceSynchronize());
   Timer tm;
   DIAG_CHECK(tm.create());
   hipEvent_t e0 = tm.e0, e1 = tm.e1;
   DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int r = 0; r < reps; ++r) launch();
+  for (int r = 0; r < reps; ++r) launch(-1);
   DIAG_CHECK(hipEventRecord(e1, nullptr));
   DIAG_CHECK(hipEventSynchronize(e1));
   DIAG_CHECK(hipGetLastError());
@@ -3120,9 +3236,9 @@ int diag_lds_test(int device, int rounds, uint32_t seed, int inject_block, unsig
 
 // L2 read bandwidth per XCD: 8 slices of `slice_bytes` (one per XCD id), `passes` reads of its slice by
 // every workgroup, `blocks_per_cu` workgroups of 4 waves per CU.  *tbs = aggregate bytes read / timed launch; cu_map as
-// diag_mfma_burn_map's (BURN_SLOTS x 3).
-int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
-                      unsigned long long* errors, unsigned long long* cu_map) {
+// diag_mfma_burn_map's (BURN_SLOTS x 3).  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word.
+int diag_l2_bandwidth_x(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
+                        long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map) {
   if (slice_bytes < 4096 || slice_bytes > (64u << 20) || slice_bytes % 16 || passes < 1 || passes > 1024 ||
       blocks_per_cu < 1 || blocks_per_cu > 8) {
     g_err = "l2_bandwidth: 4 KiB <= slice_bytes <= 64 MiB (multiple of 16), 1 <= passes <= 1024, 1..8 blocks/CU";
@@ -3138,6 +3254,7 @@ int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per
   DIAG_CHECK(dmap.alloc(device, map_bytes));
   hipLaunchKernelGGL(l2_fill_kernel, dim3(1024), dim3(256), 0, nullptr, static_cast<uint4*>(dbuf.ptr), n_vec, seed);
   DIAG_CHECK(hipGetLastError());
+  if (const int rc = flip_slice_word(dbuf.ptr, slice_vec, inject_xcd, inject_word, "l2_bandwidth")) return rc;
   const int blocks = grid_for(device, blocks_per_cu);
   auto launch = [&]() {
     hipLaunchKernelGGL(l2_read_kernel, dim3(blocks), dim3(256), 0, nullptr, static_cast<const uint4*>(dbuf.ptr),
@@ -3166,12 +3283,19 @@ int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per
   return 0;
 }
 
+int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
+                      unsigned long long* errors, unsigned long long* cu_map) {
+  return diag_l2_bandwidth_x(device, slice_bytes, passes, blocks_per_cu, seed, -1, 0, tbs, errors, cu_map);
+}
+
 // HBM per XCD (hbm_xcd_kernel): `slice_bytes` per XCD (8 slices, a multiple of 128 KiB, at most 512 MiB),
 // read `passes` times by the XCD's own workgroups, all XCDs at once: aggregate read TB/s, wrong words,
 // per-CU map.  With `xcd_tbs` (8 doubles) each XCD then streams its slice alone: its own read TB/s (0 for an
-// XCD without CUs on this device).
-int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
-                 unsigned long long* errors, unsigned long long* cu_map, double* xcd_tbs) {
+// XCD without CUs on this device).  *errors counts the timed full-chip run and the lone runs; cu_map is the timed
+// full-chip run's.  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word.
+int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
+                   long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map,
+                   double* xcd_tbs) {
   const size_t chunk = static_cast<size_t>(HBM_XCD_CHUNK_VEC) * 16;
   if (slice_bytes < chunk || slice_bytes > (512u << 20) || slice_bytes % chunk || passes < 1 || passes > 64 ||
       blocks_per_cu < 1 || blocks_per_cu > 8) {
@@ -3189,6 +3313,7 @@ int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, 
   DIAG_CHECK(dmap.alloc(device, map_bytes));
   hipLaunchKernelGGL(l2_fill_kernel, dim3(4096), dim3(256), 0, nullptr, static_cast<uint4*>(dbuf.ptr), n_vec, seed);
   DIAG_CHECK(hipGetLastError());
+  if (const int rc = flip_slice_word(dbuf.ptr, slice_vec, inject_xcd, inject_word, "hbm_xcd")) return rc;
   const int blocks = grid_for(device, blocks_per_cu);
   Timer tm;
   DIAG_CHECK(tm.create());
@@ -3245,6 +3370,11 @@ int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, 
   }
   DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
+}
+
+int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
+                 unsigned long long* errors, unsigned long long* cu_map, double* xcd_tbs) {
+  return diag_hbm_xcd_x(device, slice_bytes, passes, blocks_per_cu, seed, -1, 0, tbs, errors, cu_map, xcd_tbs);
 }
 
 // Host link check: pinned host <-> device copies of `bytes`, `iters` each way (SDMA over PCIe),

@@ -308,6 +308,10 @@ def lib() -> ctypes.CDLL:
         for f in ("diag_gemm_bf16_x", "diag_gemm_fp8_x"):
             getattr(L, f).argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong, ctypes.c_double] + \
                 [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(ctypes.c_longlong)]
+        for f in ("diag_gemm_bf16_x2", "diag_gemm_fp8_x2"):
+            getattr(L, f).argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong, ctypes.c_double, ctypes.c_double] + \
+                [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(ctypes.c_longlong),
+                                                         ctypes.POINTER(ctypes.c_double)]
         L.diag_gemm_fp4_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.diag_gemm_fp8_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -318,6 +322,9 @@ def lib() -> ctypes.CDLL:
                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.diag_hbm_bandwidth.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int] + \
             [ctypes.POINTER(ctypes.c_double)] * 3
+        L.diag_hbm_bandwidth_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong,
+                                           ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 3 + \
+            [ctypes.POINTER(ctypes.c_ulonglong)]
         L.diag_memtest.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
                                    ctypes.POINTER(ctypes.c_double)]
@@ -326,11 +333,18 @@ def lib() -> ctypes.CDLL:
         L.diag_mfma_burn_map.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
                                          ctypes.POINTER(ctypes.c_ulonglong)]
+        L.diag_mfma_burn_map_x.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_double),
+                                                                ctypes.POINTER(ctypes.c_ulonglong),
+                                                                ctypes.POINTER(ctypes.c_ulonglong)]
         L.diag_mfma_burn_slots.restype = ctypes.c_int
         L.diag_l2_bandwidth.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
                                         ctypes.POINTER(ctypes.c_ulonglong)]
         L.diag_hbm_xcd.argtypes = list(L.diag_l2_bandwidth.argtypes) + [ctypes.POINTER(ctypes.c_double)]
+        L.diag_l2_bandwidth_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                                          ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+        L.diag_hbm_xcd_x.argtypes = list(L.diag_l2_bandwidth_x.argtypes) + [ctypes.POINTER(ctypes.c_double)]
         L.diag_lds_test.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
@@ -342,6 +356,10 @@ def lib() -> ctypes.CDLL:
         L.diag_memtest_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong,
                                      ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
                                      ctypes.POINTER(ctypes.c_double)]
+        L.diag_memtest_x2.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong,
+                                      ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
+                                      ctypes.POINTER(ctypes.c_double)]
         L.diag_poll_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_int),
                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         L.diag_p2p_copy_t.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_double,
@@ -521,13 +539,19 @@ def _ref(test: str, key: Any, scale: float) -> float:
 
 
 def _checked_gemm(fn: str, device: int, size: int, warmup: int, iters: int, samples: int,
-                  inject_elem: Optional[int], ck_tol: float) -> Tuple[float, float, float, float, List[int]]:
+                  inject_elem: Optional[int], ck_tol: float,
+                  inject_delta: Optional[float] = None) -> Tuple[float, float, float, float, List[int], float]:
+    """``fn`` is the ``_x2`` entry point: as ``_x`` plus ``inject_delta`` (NaN = the 1e6 overwrite) and the
+    checksums' absolute floor."""
     tf, err, ms, ck = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    floor = ctypes.c_double()
     out = (ctypes.c_longlong * 12)()
     _check(getattr(lib(), fn)(device, size, size, size, warmup, iters, samples,
-                              -1 if inject_elem is None else int(inject_elem), ck_tol, ctypes.byref(tf),
-                              ctypes.byref(err), ctypes.byref(ms), ctypes.byref(ck), out))
-    return tf.value, err.value, ms.value, ck.value, list(out)
+                              -1 if inject_elem is None else int(inject_elem),
+                              float("nan") if inject_delta is None else float(inject_delta), ck_tol,
+                              ctypes.byref(tf), ctypes.byref(err), ctypes.byref(ms), ctypes.byref(ck), out,
+                              ctypes.byref(floor)))
+    return tf.value, err.value, ms.value, ck.value, list(out), floor.value
 
 
 def _gemm_output(dt: int, size: int) -> str:
@@ -539,9 +563,12 @@ def _gemm_output(dt: int, size: int) -> str:
     return "bf16+colsums" if probe(dt, size, size) else "fp32"
 
 
-def _checksum_verdict(res: Dict[str, Any], ck_err: float, out: List[int], tol: float) -> str:
-    """Record the tile checksums in ``res``; a non-empty string describes the tiles that failed them."""
+def _checksum_verdict(res: Dict[str, Any], ck_err: float, out: List[int], tol: float, floor: float) -> str:
+    """Record the tile checksums in ``res``; a non-empty string describes the tiles that failed them.
+    ``checksum_floor`` = ``tol`` x the largest column magnitude sum|a*b|: the absolute error of one output that is
+    flagged whichever column it is in."""
     res["checksum_err"] = ck_err
+    res["checksum_floor"] = floor
     res["checksum_bad_tiles"] = out[0]
     if not out[0]:
         return ""
@@ -555,67 +582,82 @@ def _checksum_verdict(res: Dict[str, Any], ck_err: float, out: List[int], tol: f
 
 
 def gemm(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20, samples: int = 4096,
-         scale: Scale = FULL, inject_elem: Optional[int] = None) -> Dict[str, Any]:
+         scale: Scale = FULL, inject_elem: Optional[int] = None,
+         inject_delta: Optional[float] = None) -> Dict[str, Any]:
     """bf16 GEMM burn-in: rate, sampled fp32-reference error, and every output tile checked by its column
     checksums (a bad tile is named with the XCD that computed it).  ``inject_elem`` (a test hook) overwrites
-    that output between the timing and the checks.
+    that output between the timing and the checks, with 1e6 or, given ``inject_delta``, with its value + delta.
 
     At 256-multiple sizes that fill the chip the timed kernel writes bf16 C -- the output hipBLASLt writes, so
     the rate compares like for like -- and forms the column sums itself, in fp64 from its fp32 accumulators
     (``gemm_launch_ck``); the sampled error is then what lies beyond the bf16 rounding of the output."""
     t0 = time.perf_counter()
-    tf, err, ms, ck, out = _checked_gemm("diag_gemm_bf16_x", device, size, warmup, iters, samples, inject_elem,
-                                         GEMM_CK_TOL)
+    tf, err, ms, ck, out, floor = _checked_gemm("diag_gemm_bf16_x2", device, size, warmup, iters, samples,
+                                                inject_elem, GEMM_CK_TOL, inject_delta)
     res = {"tflops": round(tf, 1), "max_rel_err": err, "ms_per_gemm": round(ms, 4),
            "shape": [size, size, size], "output": _gemm_output(0, size),
            "wall_s": round(time.perf_counter() - t0, 3)}
     problems = [f"rel err {err:.2e} > {GEMM_MAX_REL_ERR:g}"] if not err <= GEMM_MAX_REL_ERR else []
-    bad = _checksum_verdict(res, ck, out, GEMM_CK_TOL)
+    bad = _checksum_verdict(res, ck, out, GEMM_CK_TOL, floor)
     problems += [bad] if bad else []
     return _rated(res, {"tflops": tf}, {"tflops": _ref("gemm", size, scale.compute)}, "TFLOP/s",
                   not problems, "; ".join(problems))
 
 
 def gemm_fp8(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20,
-             samples: int = 4096, scale: Scale = FULL, inject_elem: Optional[int] = None) -> Dict[str, Any]:
+             samples: int = 4096, scale: Scale = FULL, inject_elem: Optional[int] = None,
+             inject_delta: Optional[float] = None) -> Dict[str, Any]:
     """MX-fp8 GEMM burn-in: rate, sampled fp64-reference error (normalised by sum|a*b|) and the tile
-    checksums of every output, as ``gemm`` (bf16 C with fused column sums)."""
+    checksums of every output, as ``gemm`` (bf16 C with fused column sums; the same test hooks)."""
     t0 = time.perf_counter()
-    tf, err, ms, ck, out = _checked_gemm("diag_gemm_fp8_x", device, size, warmup, iters, samples, inject_elem,
-                                         GEMM_FP8_CK_TOL)
+    tf, err, ms, ck, out, floor = _checked_gemm("diag_gemm_fp8_x2", device, size, warmup, iters, samples,
+                                                inject_elem, GEMM_FP8_CK_TOL, inject_delta)
     res = {"tflops": round(tf, 1), "max_err_over_mag": err, "ms_per_gemm": round(ms, 4),
            "shape": [size, size, size], "output": _gemm_output(1, size),
            "wall_s": round(time.perf_counter() - t0, 3)}
     problems = [f"err {err:.2e} > {GEMM_FP8_MAX_ERR:g}"] if not err <= GEMM_FP8_MAX_ERR else []
-    bad = _checksum_verdict(res, ck, out, GEMM_FP8_CK_TOL)
+    bad = _checksum_verdict(res, ck, out, GEMM_FP8_CK_TOL, floor)
     problems += [bad] if bad else []
     return _rated(res, {"tflops": tf}, {"tflops": _ref("gemm_fp8", size, scale.compute)}, "TFLOP/s",
                   not problems, "; ".join(problems))
 
 
-def hbm(device: int = 0, gib: float = 4.0, iters: int = 10, scale: Scale = FULL) -> Dict[str, Any]:
-    c, r, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+def hbm(device: int = 0, gib: float = 4.0, iters: int = 10, scale: Scale = FULL,
+        inject_word: Optional[int] = None, inject_phase: str = "copy") -> Dict[str, Any]:
+    """HBM copy / read / write streams over ``gib`` per buffer, and the bytes behind the rates: after the copy phase
+    every 16-byte element of the destination must hold the source's fill, after the write phase the written value
+    (``errors``: elements that do not; checked outside the timed loops).  ``inject_word`` (a test hook) overwrites
+    that element of the destination before the check of ``inject_phase`` (``"copy"`` or ``"write"``)."""
+    c, r, w, errs = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_ulonglong()
     t0 = time.perf_counter()
-    _check(lib().diag_hbm_bandwidth(device, int(gib * (1 << 30)), iters, ctypes.byref(c), ctypes.byref(r),
-                                    ctypes.byref(w)))
+    _check(lib().diag_hbm_bandwidth_x(device, int(gib * (1 << 30)), iters,
+                                      -1 if inject_word is None else int(inject_word),
+                                      {"copy": 0, "write": 1}[inject_phase], ctypes.byref(c), ctypes.byref(r),
+                                      ctypes.byref(w), ctypes.byref(errs)))
     res = {"copy_tbs": round(c.value, 3), "read_tbs": round(r.value, 3), "write_tbs": round(w.value, 3),
-           "gib": gib, "wall_s": round(time.perf_counter() - t0, 3)}
+           "errors": errs.value, "gib": gib, "wall_s": round(time.perf_counter() - t0, 3)}
     exp = {k: v * scale.memory for k, v in REFERENCE_RATES["hbm"].items()}
-    return _rated(res, {"copy_tbs": c.value, "read_tbs": r.value}, exp, "TB/s")
+    return _rated(res, {"copy_tbs": c.value, "read_tbs": r.value}, exp, "TB/s", not errs.value,
+                  f"{errs.value} wrong 16-byte elements after the copy / write streams")
 
 
 def memtest(device: int = 0, gib: float = 8.0, passes: int = 1, seed: int = 0x5EED,
-            inject_word: Optional[int] = None) -> Dict[str, Any]:
+            inject_word: Optional[int] = None, inject_word2: Optional[int] = None, inject_pass: int = 0,
+            inject_invert: bool = False) -> Dict[str, Any]:
     """Pattern + inverse over ``gib`` of HBM, every word checked.  ``inject_word`` (a test hook) overwrites that
-    16-byte word between the first write and its check, to show a corrupted word is counted and located."""
+    16-byte word between a write and its check, to show a corrupted word is counted and located: the write of pass
+    ``inject_pass``, its inverted half with ``inject_invert``; ``inject_word2`` is a second word of that write."""
     errs, first, gbps = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_double()
     t0 = time.perf_counter()
-    if inject_word is None:
+    if inject_word is None and inject_word2 is None:
         _check(lib().diag_memtest(device, int(gib * (1 << 30)), seed, passes, ctypes.byref(errs),
                                   ctypes.byref(first), ctypes.byref(gbps)))
     else:
-        _check(lib().diag_memtest_x(device, int(gib * (1 << 30)), seed, passes, inject_word, ctypes.byref(errs),
-                                    ctypes.byref(first), ctypes.byref(gbps)))
+        _check(lib().diag_memtest_x2(device, int(gib * (1 << 30)), seed, passes,
+                                     -1 if inject_word is None else int(inject_word),
+                                     -1 if inject_word2 is None else int(inject_word2), inject_pass,
+                                     1 if inject_invert else 0, ctypes.byref(errs), ctypes.byref(first),
+                                     ctypes.byref(gbps)))
     ok = errs.value <= MEMTEST_MAX_ERRORS
     res: Dict[str, Any] = {"pass": ok, "errors": errs.value, "gib": gib, "passes": passes,
                            "gbps": round(gbps.value, 1), "wall_s": round(time.perf_counter() - t0, 3),
@@ -701,10 +743,12 @@ def cu_map_summary(maps: Dict[str, Any]) -> Dict[str, Any]:
 
 
 def mfma_burn(device: int = 0, kinds=MFMA_KINDS, iters: int = 2000, reps: int = 5,
-              scale: Scale = FULL) -> Dict[str, Any]:
+              scale: Scale = FULL, inject_block: int = -1) -> Dict[str, Any]:
     """Every matrix-core precision of the MI355X: dense TFLOP/s and exact-result errors per kind, plus
     where on the chip the waves ran (:func:`cu_map_summary`): the CU behind any wrong result, and an XCD
-    whose waves fall more than ``XCD_SLOW_RATIO`` behind the others (degraded)."""
+    whose waves fall more than ``XCD_SLOW_RATIO`` behind the others (degraded).  ``inject_block`` (a test hook)
+    makes one lane of that workgroup wrong in the warm-up launch of every kind (the result then carries
+    ``cu_maps``, the raw per-slot tables by kind)."""
     t0 = time.perf_counter()
     rows: Dict[str, Any] = {}
     rates: Dict[str, float] = {}
@@ -715,8 +759,12 @@ def mfma_burn(device: int = 0, kinds=MFMA_KINDS, iters: int = 2000, reps: int = 
     for kind in kinds:
         tf, errs = ctypes.c_double(), ctypes.c_ulonglong()
         m = (ctypes.c_ulonglong * (3 * nslots))()
-        _check(L.diag_mfma_burn_map(device, MFMA_KINDS.index(kind), iters, reps, ctypes.byref(tf),
-                                    ctypes.byref(errs), m))
+        if inject_block < 0:
+            _check(L.diag_mfma_burn_map(device, MFMA_KINDS.index(kind), iters, reps, ctypes.byref(tf),
+                                        ctypes.byref(errs), m))
+        else:
+            _check(L.diag_mfma_burn_map_x(device, MFMA_KINDS.index(kind), iters, reps, inject_block,
+                                          ctypes.byref(tf), ctypes.byref(errs), m))
         maps[kind] = list(m)
         rows[kind] = {"tflops": round(tf.value, 1), "errors": errs.value}
         rates[kind] = tf.value
@@ -728,6 +776,8 @@ def mfma_burn(device: int = 0, kinds=MFMA_KINDS, iters: int = 2000, reps: int = 
     exp = {k: REFERENCE_RATES["mfma"][k] * scale.compute for k in kinds}
     res = _rated({"kinds": rows, "map": where, "wall_s": round(time.perf_counter() - t0, 3)}, rates, exp,
                  "TFLOP/s", not wrong, "; ".join(wrong))
+    if inject_block >= 0:
+        res["cu_maps"] = maps
     return _lag_verdict(res, where, "waves")
 
 
@@ -777,49 +827,67 @@ def lds_test(device: int = 0, rounds: int = 4, seed: int = 0x1D5, inject_block: 
 
 
 def l2_bandwidth(device: int = 0, slice_kib: int = 2048, passes: int = 32, blocks_per_cu: int = 8,
-                 seed: int = 0x12C3, scale: Scale = FULL) -> Dict[str, Any]:
+                 seed: int = 0x12C3, scale: Scale = FULL, inject_xcd: int = -1,
+                 inject_word: int = 0) -> Dict[str, Any]:
     """Each XCD's 4 MiB L2, read by that XCD's own CUs (a ``slice_kib`` slice per XCD, every word checked):
     aggregate TB/s against the reference, per-XCD wave time against the median XCD (degraded beyond
-    ``XCD_SLOW_RATIO``: an L2 that lost ways or a slow XCD), wrong words located to the CU."""
+    ``XCD_SLOW_RATIO``: an L2 that lost ways or a slow XCD), wrong words located to the CU.  ``inject_xcd`` /
+    ``inject_word`` (a test hook) flip one bit of that 32-bit word of that XCD's slice before the first read;
+    the result then carries ``cu_map``, the raw per-slot table (waves, wrong words, ticks) x slots."""
     L = lib()
     nslots = L.diag_mfma_burn_slots()
     tbs, errs = ctypes.c_double(), ctypes.c_ulonglong()
     m = (ctypes.c_ulonglong * (3 * nslots))()
     t0 = time.perf_counter()
-    _check(L.diag_l2_bandwidth(device, slice_kib << 10, passes, blocks_per_cu, seed, ctypes.byref(tbs),
-                               ctypes.byref(errs), m))
+    if inject_xcd < 0:
+        _check(L.diag_l2_bandwidth(device, slice_kib << 10, passes, blocks_per_cu, seed, ctypes.byref(tbs),
+                                   ctypes.byref(errs), m))
+    else:
+        _check(L.diag_l2_bandwidth_x(device, slice_kib << 10, passes, blocks_per_cu, seed, inject_xcd, inject_word,
+                                     ctypes.byref(tbs), ctypes.byref(errs), m))
     where = cu_map_summary({"l2": list(m)})
     wrong = f"{errs.value} wrong words on " + ", ".join(where.get("bad_cus", [])[:4]) if errs.value else ""
     exp = {"read_tbs": REFERENCE_RATES["l2"]["read_tbs"] * scale.compute}
     res = _rated({"read_tbs": round(tbs.value, 2), "errors": errs.value, "map": where,
                   "wall_s": round(time.perf_counter() - t0, 3)}, {"read_tbs": tbs.value}, exp, "TB/s",
                  not errs.value, wrong)
+    if inject_xcd >= 0:
+        res["cu_map"] = list(m)
     return _lag_verdict(res, where, "L2 reads")
 
 
 def hbm_xcd(device: int = 0, slice_mib: int = 256, passes: int = 4, blocks_per_cu: int = 4,
-            seed: int = 0x4B3D, scale: Scale = FULL) -> Dict[str, Any]:
+            seed: int = 0x4B3D, scale: Scale = FULL, inject_xcd: int = -1, inject_word: int = 0) -> Dict[str, Any]:
     """HBM reads per XCD.  Each XCD streams its own ``slice_mib`` slice (8 of them, far past the L2s and the
     MALL) with its own workgroups, every word checked: first all XCDs together (aggregate read TB/s), then
     each XCD alone (``alone_tbs``: that XCD's own path to the memory stacks).  All XCDs together saturate
     HBM, so the aggregate hides one slow XCD; alone, every XCD of a healthy MI355X reads at 1.28-1.33 TB/s
     (spread < 3 %, profiles/hbm_xcd_explore_mi355x.json).  Judged: the aggregate against the HBM-read
     reference, the slowest XCD alone against the per-XCD reference, and an XCD below
-    ``XCD_ALONE_MIN_RATIO`` of the median XCD is degraded even when above the floor."""
+    ``XCD_ALONE_MIN_RATIO`` of the median XCD is degraded even when above the floor.  ``errors`` counts the timed
+    run of all XCDs and the lone runs; the map is the timed run's.  ``inject_xcd`` / ``inject_word`` (a test hook)
+    flip one bit of that 32-bit word of that XCD's slice before the first read (the result then carries ``cu_map``,
+    the raw per-slot table)."""
     L = lib()
     nslots = L.diag_mfma_burn_slots()
     tbs, errs = ctypes.c_double(), ctypes.c_ulonglong()
     m = (ctypes.c_ulonglong * (3 * nslots))()
     alone = (ctypes.c_double * 8)()
     t0 = time.perf_counter()
-    _check(L.diag_hbm_xcd(device, slice_mib << 20, passes, blocks_per_cu, seed, ctypes.byref(tbs),
-                          ctypes.byref(errs), m, alone))
+    if inject_xcd < 0:
+        _check(L.diag_hbm_xcd(device, slice_mib << 20, passes, blocks_per_cu, seed, ctypes.byref(tbs),
+                              ctypes.byref(errs), m, alone))
+    else:
+        _check(L.diag_hbm_xcd_x(device, slice_mib << 20, passes, blocks_per_cu, seed, inject_xcd, inject_word,
+                                ctypes.byref(tbs), ctypes.byref(errs), m, alone))
     where = cu_map_summary({"hbm_xcd": list(m)})
     # under contention the XCDs' shares of HBM are not even (measured 1.02-1.29x between runs): reported only
     where = {k: v for k, v in where.items() if k in ("cus", "xcds", "bad_cus")}
     per = {x: alone[x] for x in range(8) if alone[x] > 0}
     res: Dict[str, Any] = {"read_tbs": round(tbs.value, 3), "errors": errs.value,
                            "alone_tbs": {str(x): round(v, 3) for x, v in per.items()}, "map": where}
+    if inject_xcd >= 0:
+        res["cu_map"] = list(m)
     rates = {"read_tbs": tbs.value}
     exp = {"read_tbs": REFERENCE_RATES["hbm_xcd"]["read_tbs"] * scale.memory}
     notes = []

@@ -194,6 +194,16 @@ class FakeDiagLib:
             self._checksums("gemm_fp8", device, inject, ck_err, out)
         return rc
 
+    def diag_gemm_bf16_x2(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err,
+                          out, floor):
+        _put(floor, ctypes.c_double, max(tol, 0.0) * 5.2e5)  # tol x the largest column sum|a*b|
+        return self.diag_gemm_bf16_x(device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out)
+
+    def diag_gemm_fp8_x2(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err,
+                         out, floor):
+        _put(floor, ctypes.c_double, max(tol, 0.0) * 5.2e5)
+        return self.diag_gemm_fp8_x(device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out)
+
     def diag_gemm_fp8(self, device, m, n, k, warmup, iters, samples, tflops, err, ms):
         return self._gemm("gemm_fp8", device, m, tflops, err, ms)
 
@@ -204,6 +214,10 @@ class FakeDiagLib:
         _put(r, ctypes.c_double, f * self.ref["hbm"]["read_tbs"])
         _put(w, ctypes.c_double, f * 6.9)
         return self.rc
+
+    def diag_hbm_bandwidth_x(self, device, nbytes, iters, inject_word, inject_phase, c, r, w, errs):
+        _put(errs, ctypes.c_ulonglong, 1 if inject_word >= 0 else 0)
+        return self.diag_hbm_bandwidth(device, nbytes, iters, c, r, w)
 
     def diag_memtest(self, device, nbytes, seed, passes, errs, first, gbps):
         self._log(device, "memtest")
@@ -435,7 +449,8 @@ class NarrowedDiagLib:
     (what a per-device diagnostic child of the agent sees, agent/isolation.narrow_to)."""
 
     _PER_DEVICE = frozenset(("diag_device_arch", "diag_gemm_bf16", "diag_gemm_bf16_x", "diag_gemm_fp8_x",
-                             "diag_gemm_fp8", "diag_hbm_bandwidth", "diag_memtest", "diag_memtest_x", "diag_mfma_burn",
+                             "diag_gemm_fp8", "diag_gemm_bf16_x2", "diag_gemm_fp8_x2", "diag_hbm_bandwidth",
+                             "diag_hbm_bandwidth_x", "diag_memtest", "diag_memtest_x", "diag_mfma_burn",
                              "diag_mfma_burn_map", "diag_l2_bandwidth", "diag_hbm_xcd", "diag_lds_test",
                              "diag_host_link", "diag_poll_selftest"))
 

@@ -133,6 +133,19 @@ def test_gemm_tiles_failing_their_checksums_fail_the_gpu_and_name_the_xcd(fake):
     assert not r["pass"] and r["checksum_bad_tiles"] == 1 and r["checksum_first_bad_tile"] == [0, 0]
 
 
+def test_hbm_wrong_bytes_fail_at_full_rate_and_are_not_remeasured(fake):
+    """The HBM streams' bytes are checked: a wrong element fails the test whatever the rates (a copy that skipped
+    bytes would report a better one), as numerics, so it is not measured again; the GEMMs report their floor."""
+    lib = fake()
+    r = diag.hbm(0)
+    assert r["pass"] and r["errors"] == 0 and r["numerics"] == "", r
+    r = diag.hbm(0, inject_word=7, inject_phase="write")
+    assert not r["pass"] and r["errors"] == 1 and r["fraction"] >= 1.0, r
+    assert r["detail"] == "1 wrong 16-byte elements after the copy / write streams" and not diag._slow_only(r), r
+    assert lib.calls.count("hbm") == 2
+    assert 0 < diag.gemm(0)["checksum_floor"] < 1 and diag.gemm_fp8(0)["checksum_floor"] > 0
+
+
 def test_cpx_partition_at_one_eighth_is_healthy(fake):
     # CPX: 32 CUs, NPS1 (all of HBM addressable, an eighth of the bandwidth share); every rate 1/8
     lib = fake(rate=1 / 8, cus=32, link=(57.2 / 8, 56.8 / 8),

@@ -83,3 +83,43 @@ def test_real_annotation_is_parsed_natively():
     rep = fixtures.mi355x_probe_report("n", gpus=8)
     raw = fixtures.health_annotation(rep)["amd.com/mi355x-health"]
     assert fastpath.ext().loads(raw) == json.loads(raw) == rep
+
+
+# The self-test hooks of the active diagnostics (csrc/diag/diag.hip): each `_x` entry point is exported next to the
+# entry point the agent calls, and ops/diag.py declares as many ctypes arguments as the C signature has.
+DIAG_HOOKS = {"diag_gemm_bf16_x": "diag_gemm_bf16", "diag_gemm_fp8_x": "diag_gemm_fp8",
+              "diag_gemm_bf16_x2": "diag_gemm_bf16_x", "diag_gemm_fp8_x2": "diag_gemm_fp8_x",
+              "diag_memtest_x": "diag_memtest", "diag_memtest_x2": "diag_memtest_x",
+              "diag_hbm_bandwidth_x": "diag_hbm_bandwidth", "diag_mfma_burn_map_x": "diag_mfma_burn_map",
+              "diag_l2_bandwidth_x": "diag_l2_bandwidth", "diag_hbm_xcd_x": "diag_hbm_xcd"}
+
+
+def _c_parameters(source, name):
+    import re
+    m = re.search(r"^int " + name + r"\(([^)]*)\)\s*\{", source, re.M)
+    assert m, f"{name} is not defined in diag.hip"
+    return [p.strip() for p in m.group(1).split(",")]
+
+
+@pytest.mark.parametrize("hook", sorted(DIAG_HOOKS))
+def test_diag_hook_entry_points_match_their_ctypes_signatures(hook, monkeypatch):
+    import ctypes
+    import os
+
+    from k8s_gpu_node_checker_amd.ops import diag, native
+    if not os.path.exists(os.path.join(native.NATIVE_DIR, "libmi355x_diag.so")):
+        pytest.skip("libmi355x_diag.so not built (no hipcc)")
+    monkeypatch.setattr(diag, "_lib", None)  # the real library, whatever another test installed
+    L = diag.lib()
+    assert isinstance(L, ctypes.CDLL)
+    with open(os.path.join(os.path.dirname(diag.__file__), "..", "csrc", "diag", "diag.hip")) as f:
+        source = f.read()
+    for name in (hook, DIAG_HOOKS[hook]):
+        params = _c_parameters(source, name)
+        fn = getattr(L, name)  # AttributeError: not exported
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, params, fn.argtypes)
+        for p, t in zip(params, fn.argtypes):
+            assert ("*" in p) == (isinstance(t, type) and issubclass(t, (ctypes._Pointer, ctypes.c_void_p))), (name, p, t)
+    # the thin wrapper keeps the agent's signature: the hook adds parameters, it drops none
+    base, ext = _c_parameters(source, DIAG_HOOKS[hook]), _c_parameters(source, hook)
+    assert set(base) <= set(ext), (base, ext)
