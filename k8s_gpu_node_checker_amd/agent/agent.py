@@ -1131,7 +1131,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--source", choices=("auto", "native", "python", "fixture"), default="auto")
     ap.add_argument("--fixture", help="recorded probe report (source=fixture)")
     ap.add_argument("--interval", type=float, default=60.0)
-    ap.add_argument("--diag-level", type=int, default=0, choices=(0, 1, 2))
+    ap.add_argument("--diag-level", type=int, default=0, choices=(0, 1, 2, 3),
+                    help="0 off, 1 quick, 2 deep, 3 deep plus the vector ALU and the vector register files")
     ap.add_argument("--diag-interval", type=float, default=3600.0)
     ap.add_argument("--publish", default="annotation", help="comma list of annotation,http,stdout")
     ap.add_argument("--listen", default="0.0.0.0:9464")

@@ -78,7 +78,7 @@ def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="mi355x-node-cycle", description=__doc__.splitlines()[0])
     ap.add_argument("--devices", required=True, help="comma list of HIP ordinals")
-    ap.add_argument("--level", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--level", type=int, default=1, choices=(1, 2, 3))
     ap.add_argument("--timeout", type=float, default=150.0, help="per-device watchdog and RCCL deadline (s)")
     ap.add_argument("--parallel", type=int, default=8)
     ap.add_argument("--no-fabric", dest="fabric", action="store_false")

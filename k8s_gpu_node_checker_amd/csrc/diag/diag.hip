@@ -28,6 +28,10 @@
 //   host_link   pinned host <-> device copy bandwidth over the PCIe link.
 //   mfma_burn   matrix-core datapath burn-in per precision (bf16, fp8, MX-fp8,
 //               MX-fp4), register-resident, every lane's exact result checked.
+//   regfile     both vector register files of every SIMD (512 registers x 64
+//               lanes) under four patterns, errors located to the SIMD.
+//   valu_burn   vector-ALU burn-in (fp64 FMA, packed fp32 FMA, 32-bit integer
+//               multiply-add), every lane bit-exact against the host (valu_ref.h).
 //
 // C ABI (ctypes, ops/diag.py).  Every HIP call is checked; on failure the
 // function returns a negative code and diag_last_error() says what failed.
@@ -1809,6 +1813,177 @@ __global__ void __launch_bounds__(1024) lds_test_kernel(uint32_t words, uint32_t
 }
 
 // ---------------------------------------------------------------------------
+// Register-file test: each SIMD of gfx950 holds 512 registers x 64 lanes x 4 B = 128 KiB (256 VGPRs and 256 AGPRs per
+// wave at one wave per SIMD) -- more SRAM per chip than the LDS and the L2 together.  A workgroup of four waves at 512
+// registers each takes a whole CU, one wave per SIMD.  Every tested register of every lane takes four patterns in
+// turn (a value distinct per register, lane, workgroup and seed; its inverse; 0x55..; 0xAA..: every bit at 0 and at
+// 1); all registers of both files are written before the first is read back, with a hold in between, so a write that
+// disturbs another register or a cell that does not retain is seen.  Mismatching words are counted per lane and per
+// file and attributed to the SIMD (wave_slot() << 2 | HW_ID.SIMD_ID).
+//
+// The registers are named explicitly in one asm statement (the assembler's .set / .rept / v[sym] / a[sym]): C++
+// values kept live through operand barriers are spilled by the thousand, which would test scratch memory.  The
+// statement touches no memory.  The compiler owns v0..v(RF_VLO-1): the lane key, two temporaries, the two error
+// counts and the injection mask are its operands; every tested register is a clobber, which also makes the kernel
+// descriptor allocate all 512.  A VALU result goes through s_nop 1 before a v_accvgpr_write reads it (nothing pads
+// the inside of an asm string).  diag_regfile_test refuses to run a build whose kernel has a scratch segment.
+constexpr int RF_VLO = 8, RF_VHI = 255, RF_ALO = 0, RF_AHI = 255;
+constexpr int RF_NV = RF_VHI - RF_VLO + 1, RF_NA = RF_AHI - RF_ALO + 1;
+constexpr int RF_REGS = RF_NV + RF_NA;  // registers of one lane holding a pattern at once
+constexpr int RF_SLOTS = BURN_SLOTS * 4;
+static_assert(RF_REGS >= 500, "the register-file test must hold at least 500 of a lane's 512 registers");
+
+// "p<t>0" .. "p<t>9": ten register names of a clobber list (a range is not accepted there)
+#define RF_DEC(p, t) p #t "0", p #t "1", p #t "2", p #t "3", p #t "4", p #t "5", p #t "6", p #t "7", p #t "8", p #t "9"
+#define RF_CENT(p, h) RF_DEC(p, h##0), RF_DEC(p, h##1), RF_DEC(p, h##2), RF_DEC(p, h##3), RF_DEC(p, h##4), \
+                      RF_DEC(p, h##5), RF_DEC(p, h##6), RF_DEC(p, h##7), RF_DEC(p, h##8), RF_DEC(p, h##9)
+#define RF_TENS(p) RF_DEC(p, 1), RF_DEC(p, 2), RF_DEC(p, 3), RF_DEC(p, 4), RF_DEC(p, 5), RF_DEC(p, 6), RF_DEC(p, 7), \
+                   RF_DEC(p, 8), RF_DEC(p, 9)
+#define RF_FROM_10(p) RF_TENS(p), RF_CENT(p, 1), RF_DEC(p, 20), RF_DEC(p, 21), RF_DEC(p, 22), RF_DEC(p, 23), \
+                      RF_DEC(p, 24), p "250", p "251", p "252", p "253", p "254", p "255"
+#define RF_CLOBBERS "v8", "v9", RF_FROM_10("v"), "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", RF_FROM_10("a")
+
+// the walk over the registers: rf_r the register, rf_k its constant (rf_nk = ~rf_k), the same in write and check
+#define RF_BEGIN ".set rf_r, %[vlo]\n.set rf_k, 0x85EBCA6B\n.set rf_nk, rf_k ^ 0xffffffff\n"
+#define RF_NEXT ".set rf_r, rf_r + 1\n.set rf_k, (rf_k + 0x9E3779B1) & 0xffffffff\n.set rf_nk, rf_k ^ 0xffffffff\n"
+// EXP leaves the expected word of register rf_r in %[tmp]
+#define RF_EXP_HASH "v_add_u32 %[tmp], rf_k, %[key]\n"    // key + k(r)
+#define RF_EXP_INV "v_sub_u32 %[tmp], rf_nk, %[key]\n"    // ~(key + k(r)) = ~k(r) - key
+#define RF_EXP_55 "v_mov_b32 %[tmp], 0x55555555\n"
+#define RF_EXP_AA "v_mov_b32 %[tmp], 0xAAAAAAAA\n"
+#define RF_WRITE(EXP)                                                                                        \
+  RF_BEGIN ".rept %[nv]\n" EXP "v_mov_b32 v[rf_r], %[tmp]\n" RF_NEXT ".endr\n"                               \
+  ".set rf_r, %[alo]\n.rept %[na]\n" EXP "s_nop 1\nv_accvgpr_write_b32 a[rf_r], %[tmp]\n" RF_NEXT ".endr\n"
+#define RF_HOLD(ID)                                                                                          \
+  "s_mov_b32 %[st], %[hold]\n"                                                                               \
+  ".Lrf_hold" ID "_%=:\ns_cmp_eq_u32 %[st], 0\ns_cbranch_scc1 .Lrf_held" ID "_%=\ns_sleep 8\n"                \
+  "s_sub_u32 %[st], %[st], 1\ns_branch .Lrf_hold" ID "_%=\n.Lrf_held" ID "_%=:\n"
+#define RF_CHECK(EXP)                                                                                        \
+  RF_BEGIN ".rept %[nv]\n" EXP "v_cmp_ne_u32 vcc, %[tmp], v[rf_r]\nv_addc_co_u32 %[cv], vcc, 0, %[cv], vcc\n" \
+  RF_NEXT ".endr\n"                                                                                          \
+  ".set rf_r, %[alo]\n.rept %[na]\nv_accvgpr_read_b32 %[tmp2], a[rf_r]\n" EXP "s_nop 1\n"                    \
+  "v_cmp_ne_u32 vcc, %[tmp], %[tmp2]\nv_addc_co_u32 %[ca], vcc, 0, %[ca], vcc\n" RF_NEXT ".endr\n"
+// the self-check: %[inj] (one bit in lane 0 of wave 0 of the injected workgroup, 0 elsewhere) is XOR-ed into the
+// register %[which] selects -- 0 / 1 the lowest / highest tested VGPR, 2 / 3 the lowest / highest tested AGPR
+#define RF_INJECT_V(N, REG)                                                                                  \
+  "s_cmp_eq_u32 %[which], " N "\ns_cselect_b32 %[st], -1, 0\nv_and_b32 %[tmp], %[st], %[inj]\n"              \
+  "v_xor_b32 v[" REG "], v[" REG "], %[tmp]\n"
+#define RF_INJECT_A(N, REG)                                                                                  \
+  "s_cmp_eq_u32 %[which], " N "\ns_cselect_b32 %[st], -1, 0\nv_and_b32 %[tmp], %[st], %[inj]\n"              \
+  "v_accvgpr_read_b32 %[tmp2], a[" REG "]\ns_nop 1\nv_xor_b32 %[tmp2], %[tmp2], %[tmp]\ns_nop 1\n"           \
+  "v_accvgpr_write_b32 a[" REG "], %[tmp2]\n"
+#define RF_INJECT RF_INJECT_V("0", "%[vlo]") RF_INJECT_V("1", "%[vhi]") RF_INJECT_A("2", "%[alo]") RF_INJECT_A("3", "%[ahi]")
+
+__global__ void __launch_bounds__(256, 1) regfile_test_kernel(uint32_t seed, int hold, int inject_block, int inject_reg,
+                                                              unsigned long long* errors, unsigned long long* simd_map) {
+  static_assert(RF_VLO == 8 && RF_VHI == 255 && RF_ALO == 0 && RF_AHI == 255, "RF_CLOBBERS names v8..v255, a0..a255");
+  const unsigned lane = threadIdx.x & 63u;
+  const uint32_t key = mix32((static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x) * 0x9E3779B97F4A7C15ULL + seed);
+  const uint32_t inj = static_cast<int>(blockIdx.x) == inject_block && threadIdx.x == 0 ? 0x10u : 0u;
+  uint32_t bad_v = 0, bad_a = 0, tmp, tmp2, st;
+  asm volatile(
+      RF_WRITE(RF_EXP_HASH) RF_HOLD("0") RF_INJECT RF_CHECK(RF_EXP_HASH)
+      RF_WRITE(RF_EXP_INV) RF_HOLD("1") RF_CHECK(RF_EXP_INV)
+      RF_WRITE(RF_EXP_55) RF_HOLD("2") RF_CHECK(RF_EXP_55)
+      RF_WRITE(RF_EXP_AA) RF_HOLD("3") RF_CHECK(RF_EXP_AA)
+      : [cv] "+v"(bad_v), [ca] "+v"(bad_a), [tmp] "=&v"(tmp), [tmp2] "=&v"(tmp2), [st] "=&s"(st)
+      : [key] "v"(key), [inj] "v"(inj), [which] "s"(inject_reg), [hold] "s"(hold), [vlo] "n"(RF_VLO), [vhi] "n"(RF_VHI),
+        [alo] "n"(RF_ALO), [ahi] "n"(RF_AHI), [nv] "n"(RF_NV), [na] "n"(RF_NA)
+      : "vcc", "scc", RF_CLOBBERS);
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
+  unsigned long long* row = simd_map + 3 * ((wave_slot() << 2) | ((hw >> 4) & 3u));
+  if (lane == 0) atomicAdd(row, 1ULL);
+  if (bad_v) {
+    atomicAdd(row + 1, static_cast<unsigned long long>(bad_v));
+    atomicAdd(errors, static_cast<unsigned long long>(bad_v));
+  }
+  if (bad_a) {
+    atomicAdd(row + 2, static_cast<unsigned long long>(bad_a));
+    atomicAdd(errors, static_cast<unsigned long long>(bad_a));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Vector-ALU burn-in: the datapaths every non-GEMM kernel runs on, which no matrix-core instruction exercises.
+//   0 f64     v_fma_f64          1 pk_f32  v_pk_fma_f32          2 i32  v_mad_u64_u32 (the 32-bit multiplier)
+// Shaped like mfma_burn_kernel: register-resident, 2 workgroups of 4 waves per CU, VALU_CHAINS independent chains
+// per lane, VALU_UNROLL steps of each per iteration.  Operands differ per lane and keep every intermediate normal
+// (valu_ref.h, which also computes what each lane must end with): the device must match the host bit for bit.
+#include "valu_ref.h"  // the chains and their host expectation (host-compilable, tests/test_simd_diag_cpu.py)
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int KIND>
+struct ValuChain;
+template <>
+struct ValuChain<0> {
+  double x, a, b;
+  __device__ __forceinline__ void load(const uint64_t* o) {
+    x = __longlong_as_double(o[0]), a = __longlong_as_double(o[1]), b = __longlong_as_double(o[2]);
+  }
+  __device__ __forceinline__ void step() { x = __builtin_fma(x, a, b); }
+  __device__ __forceinline__ uint64_t bits() const { return static_cast<uint64_t>(__double_as_longlong(x)); }
+};
+template <>
+struct ValuChain<1> {
+  f32x2 x, a, b;
+  __device__ __forceinline__ void load(const uint64_t* o) {
+    __builtin_memcpy(&x, o, 8), __builtin_memcpy(&a, o + 1, 8), __builtin_memcpy(&b, o + 2, 8);
+  }
+  __device__ __forceinline__ void step() { x = __builtin_elementwise_fma(x, a, b); }
+  __device__ __forceinline__ uint64_t bits() const {
+    uint64_t u;
+    __builtin_memcpy(&u, &x, 8);
+    return u;
+  }
+};
+template <>
+struct ValuChain<2> {
+  uint64_t x, b;
+  uint32_t a;
+  __device__ __forceinline__ void load(const uint64_t* o) { x = o[0], a = static_cast<uint32_t>(o[1]), b = o[2]; }
+  __device__ __forceinline__ void step() { x = static_cast<uint64_t>(static_cast<uint32_t>(x)) * a + b; }
+  __device__ __forceinline__ uint64_t bits() const { return x; }
+};
+
+template <int KIND>
+__global__ void __launch_bounds__(256) valu_burn_kernel(const uint64_t* __restrict__ ops,
+                                                        const uint64_t* __restrict__ expect, int iters, int inject_block,
+                                                        unsigned long long* errors, unsigned long long* cu_map) {
+  const long long t0 = wall_clock64();
+  const int lane = threadIdx.x & 63;
+  ValuChain<KIND> ch[VALU_CHAINS];
+#pragma unroll
+  for (int c = 0; c < VALU_CHAINS; ++c) ch[c].load(ops + 3 * (lane * VALU_CHAINS + c));
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int u = 0; u < VALU_UNROLL; ++u) {
+#pragma unroll
+      for (int c = 0; c < VALU_CHAINS; ++c) ch[c].step();
+    }
+  }
+  bool bad = false;
+#pragma unroll
+  for (int c = 0; c < VALU_CHAINS; ++c) {
+    uint64_t got = ch[c].bits();
+    // the self-check of the verifier (diag_valu_burn_map_x): one bit of one chain of one lane is flipped
+    if (c == 0 && static_cast<int>(blockIdx.x) == inject_block && threadIdx.x == 0) got ^= 1ULL;
+    bad |= got != expect[lane * VALU_CHAINS + c];
+  }
+  if (bad) atomicAdd(errors, 1ULL);
+  if (cu_map != nullptr) {
+    const unsigned long long nbad = __popcll(__ballot(bad));
+    const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
+    if (lane == 0) {
+      unsigned long long* row = cu_map + 3 * wave_slot();
+      atomicAdd(row, 1ULL);
+      if (nbad) atomicAdd(row + 1, nbad);
+      atomicAdd(row + 2, dt);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // L2 test: each XCD has its own 4 MiB L2.  Every workgroup finds its XCD (XCC_ID) and streams that XCD's
 // private slice of the buffer (smaller than the L2) `passes` times, checking every word; after the
 // untimed first launch the slice is L2-resident, so the timed launch measures each XCD's L2 read
@@ -3231,6 +3406,128 @@ int diag_lds_test(int device, int rounds, uint32_t seed, int inject_block, unsig
   DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
   *lds_bytes = static_cast<int>(dyn);
+  return 0;
+}
+
+// Register-file test over `rounds` x CUs workgroups of four 512-register waves (one per SIMD of a CU), each word held
+// for `hold` x 512 clocks between write and read-back.  simd_map: diag_regfile_slots() x 3 (waves run, bad VGPR
+// words, bad AGPR words) per physical SIMD (wave_slot() << 2 | SIMD_ID); *regs_per_lane = registers of a lane under
+// a pattern at once; *scratch_bytes = the kernel's private segment, and anything but 0 is an error: such a build
+// would test scratch memory.  `inject_block` >= 0 (the verifier's self-check): one bit of register `inject_reg`
+// (0 / 1 lowest / highest tested VGPR, 2 / 3 lowest / highest tested AGPR) of lane 0 of wave 0 of that workgroup is
+// flipped between the write and the check of the first pattern.
+int diag_regfile_slots(void) { return RF_SLOTS; }
+
+int diag_regfile_test(int device, int rounds, uint32_t seed, int hold, int inject_block, int inject_reg,
+                      unsigned long long* errors, unsigned long long* simd_map, int* regs_per_lane, int* scratch_bytes,
+                      double* ms) {
+  if (rounds < 1 || rounds > 64 || hold < 0 || hold > 65536) {
+    g_err = "regfile_test: 1 <= rounds <= 64, 0 <= hold <= 65536";
+    return -2;
+  }
+  if (inject_block >= 0 && (inject_reg < 0 || inject_reg > 3)) {
+    g_err = "regfile_test: inject_reg 0..3 (lowest / highest VGPR, lowest / highest AGPR)";
+    return -2;
+  }
+  DIAG_CHECK(hipSetDevice(device));
+  hipFuncAttributes attr;
+  DIAG_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(regfile_test_kernel)));
+  *regs_per_lane = RF_REGS;
+  *scratch_bytes = static_cast<int>(attr.localSizeBytes);
+  if (attr.localSizeBytes != 0) {
+    g_err = "regfile_test: the kernel was built with " + std::to_string(attr.localSizeBytes) +
+            " bytes of scratch per lane: it would test memory, not registers";
+    return -3;
+  }
+  const int blocks = grid_for(device, rounds);
+  if (inject_block >= blocks) {
+    g_err = "regfile_test: inject_block outside the grid";
+    return -2;
+  }
+  const size_t map_bytes = static_cast<size_t>(RF_SLOTS) * 3 * sizeof(unsigned long long);
+  DevBuf derr, dmap;
+  DIAG_CHECK(derr.alloc(device, sizeof(unsigned long long)));
+  DIAG_CHECK(dmap.alloc(device, map_bytes));
+  DIAG_CHECK(hipMemset(derr.ptr, 0, sizeof(unsigned long long)));
+  DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  Timer tm;
+  DIAG_CHECK(tm.create());
+  hipEvent_t e0 = tm.e0, e1 = tm.e1;
+  DIAG_CHECK(hipEventRecord(e0, nullptr));
+  hipLaunchKernelGGL(regfile_test_kernel, dim3(blocks), dim3(256), 0, nullptr, seed, hold, inject_block, inject_reg,
+                     static_cast<unsigned long long*>(derr.ptr), static_cast<unsigned long long*>(dmap.ptr));
+  DIAG_CHECK(hipGetLastError());
+  DIAG_CHECK(hipEventRecord(e1, nullptr));
+  DIAG_CHECK(hipEventSynchronize(e1));
+  float t_ms = 0.f;
+  DIAG_CHECK(event_ms(e0, e1, &t_ms));
+  *ms = t_ms;
+  DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  DIAG_CHECK(hipMemcpy(simd_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Vector-ALU burn-in of one kind (0 f64, 1 pk_f32, 2 i32; valu_burn_kernel): `reps` timed launches of `iters`
+// iterations on every CU after a checked warm-up; *gops = G(FL)OP/s (an FMA or a multiply-add counts 2 per element),
+// *errors = lanes whose final values differ from the host's in any bit; cu_map as diag_mfma_burn_map's (BURN_SLOTS
+// x 3).  `inject_block` >= 0 (the verifier's self-check): lane 0 of wave 0 of that workgroup is made wrong in the
+// warm-up launch.
+int diag_valu_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* gops,
+                         unsigned long long* errors, unsigned long long* cu_map) {
+  if (kind < 0 || kind >= VALU_KINDS || iters < 1 || iters > 65536 || reps < 1) {
+    g_err = "valu_burn: kind 0..2, 1 <= iters <= 65536, reps >= 1";
+    return -2;
+  }
+  DIAG_CHECK(hipSetDevice(device));
+  const int blocks = grid_for(device, 2);  // 8 waves per CU = 2 per SIMD
+  if (inject_block >= blocks) {
+    g_err = "valu_burn: inject_block outside the grid";
+    return -2;
+  }
+  // per lane (the same in every wave, so every wave has the same answer)
+  std::vector<uint64_t> ops(3 * VALU_LANES * VALU_CHAINS), expect(VALU_LANES * VALU_CHAINS);
+  valu_tables(kind, static_cast<long>(iters) * VALU_UNROLL, ops.data(), expect.data());
+  DevBuf dops, dex, dcnt, dmap;
+  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 3 * sizeof(unsigned long long);
+  if (cu_map != nullptr) {
+    DIAG_CHECK(dmap.alloc(device, map_bytes));
+    DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  }
+  DIAG_CHECK(dops.alloc(device, ops.size() * 8));
+  DIAG_CHECK(dex.alloc(device, expect.size() * 8));
+  DIAG_CHECK(dcnt.alloc(device, sizeof(unsigned long long)));
+  DIAG_CHECK(hipMemcpy(dops.ptr, ops.data(), ops.size() * 8, hipMemcpyHostToDevice));
+  DIAG_CHECK(hipMemcpy(dex.ptr, expect.data(), expect.size() * 8, hipMemcpyHostToDevice));
+  DIAG_CHECK(hipMemset(dcnt.ptr, 0, sizeof(unsigned long long)));
+  auto launch = [&](int inj) {
+    const uint64_t* o = static_cast<const uint64_t*>(dops.ptr);
+    const uint64_t* ex = static_cast<const uint64_t*>(dex.ptr);
+    unsigned long long* c = static_cast<unsigned long long*>(dcnt.ptr);
+    unsigned long long* m = static_cast<unsigned long long*>(dmap.ptr);  // null without a map
+    switch (kind) {
+      case 0: hipLaunchKernelGGL(valu_burn_kernel<0>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m); break;
+      case 1: hipLaunchKernelGGL(valu_burn_kernel<1>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m); break;
+      default: hipLaunchKernelGGL(valu_burn_kernel<2>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m);
+    }
+  };
+  launch(inject_block < 0 ? -1 : inject_block);  // warm-up (also checked)
+  DIAG_CHECK(hipGetLastError());
+  DIAG_CHECK(hipDeviceSynchronize());
+  Timer tm;
+  DIAG_CHECK(tm.create());
+  hipEvent_t e0 = tm.e0, e1 = tm.e1;
+  DIAG_CHECK(hipEventRecord(e0, nullptr));
+  for (int r = 0; r < reps; ++r) launch(-1);
+  DIAG_CHECK(hipEventRecord(e1, nullptr));
+  DIAG_CHECK(hipEventSynchronize(e1));
+  DIAG_CHECK(hipGetLastError());
+  float ms = 0.f;
+  DIAG_CHECK(event_ms(e0, e1, &ms));
+  DIAG_CHECK(hipMemcpy(errors, dcnt.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (cu_map != nullptr) DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  const double per_step = kind == 1 ? 4.0 : 2.0;  // a float2 FMA is two FMAs
+  const double op = static_cast<double>(blocks) * 256 * iters * VALU_UNROLL * VALU_CHAINS * per_step;
+  *gops = ms > 0.f ? op * reps / (ms * 1e-3) / 1e9 : 0.0;
   return 0;
 }
 

@@ -134,6 +134,12 @@ REFERENCE_RATES: Dict[str, Dict[Any, float]] = {
     # run and 1,299 level-1 soak rounds), each XCD alone 1.23-1.33 TB/s (profiles/hbm_xcd_explore_mi355x.json,
     # profiles/soak_level1_hbm_xcd_mi355x.json)
     "hbm_xcd": {"read_tbs": 5.8, "alone_tbs": 1.28},
+    # vector-ALU burn-in, G(FL)OP/s: each the slowest of 24 healthy runs in one process / 0.97 (f64 46,593-47,981,
+    # pk_f32 102,284-104,708, i32 49,019-49,797; first cold run 47,348 / 103,104 / 49,219:
+    # profiles/valu_burn_mi355x.json).  They rest on one box (a4:00.0; a second, 0a:00.0, gave 51,065 / 105,127 /
+    # 49,354 in one cold level-3 run: 1.06 / 1.00 / 0.98): a slower healthy device shows as degraded first, and the
+    # references follow it then, as mxfp4's did
+    "valu": {"f64": 48030.0, "pk_f32": 105400.0, "i32": 50500.0},
     "l2": {"read_tbs": 30.5},                      # per-XCD L2 reads, 2 MiB slices, 8 WG/CU: 31.6-31.9 measured
                                                    # (profiles/l2_explore_mi355x.json; 34.5 TB/s is the L2's own figure)
 }
@@ -146,6 +152,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "hbm": "copy16-r1", "hbm_xcd": "xcd-slices-4pass", "l2": "xcd-l2-2mib",
     "mfma": "burn-f8f6f4-r4",    # fp8 as the unscaled f8f6f4 instruction since round 4
     "host_link": "pinned-r1",
+    "valu": "chains8x4-r1",      # 8 chains x 4 steps per iteration, 2 workgroups per CU
+    "regfile": "v8-255+a0-255",  # no rate verdict: the stamp says which registers a clean result covered
 }
 
 
@@ -171,6 +179,8 @@ GEMM_CK_TOL = 1e-7
 GEMM_FP8_CK_TOL = 1e-5
 MEMTEST_MAX_ERRORS = 0
 MFMA_KINDS = ("bf16", "fp8", "mxfp8", "mxfp4")
+VALU_KINDS = ("f64", "pk_f32", "i32")       # v_fma_f64, v_pk_fma_f32, v_mad_u64_u32 (csrc/diag/valu_ref.h)
+REGFILE_REGS = ("vgpr_lo", "vgpr_hi", "agpr_lo", "agpr_hi")  # the registers regfile_test's self-check can flip
 P2P_MIN_FRACTION_OF_MEDIAN = 0.5  # a GPU pair slower than half the node's median pair: suspect link
 # The absolute anchor of the xGMI pair matrix: one direction of one link carries lanes x Gb/s / 8 GB/s -- x16 at
 # 38 Gb/s on MI355X (amd-smi's xgmi_link_width / xgmi_link_speed, profiles/amdsmi_xgmi_link_metrics_mi355x.json), 76
@@ -348,6 +358,12 @@ def lib() -> ctypes.CDLL:
         L.diag_lds_test.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        L.diag_regfile_slots.restype = ctypes.c_int
+        L.diag_regfile_test.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong),
+                                        ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        L.diag_valu_burn_map_x.argtypes = list(L.diag_mfma_burn_map_x.argtypes)
         L.diag_host_link.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double)]
         L.diag_p2p_copy.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
@@ -826,6 +842,80 @@ def lds_test(device: int = 0, rounds: int = 4, seed: int = 0x1D5, inject_block: 
     return res
 
 
+def simd_name(row: int) -> str:
+    """``xcd3/se1/cu5/simd2`` of a register-file map row (``wave_slot() << 2 | HW_ID.SIMD_ID``)."""
+    return f"{slot_name(row >> 2)}/simd{row & 3}"
+
+
+def regfile_test(device: int = 0, rounds: int = 2, seed: int = 0x51D, hold: int = 32, inject_block: int = -1,
+                 inject_reg: str = "vgpr_lo") -> Dict[str, Any]:
+    """Both vector register files of every SIMD (256 VGPRs + 256 AGPRs x 64 lanes = 128 KiB) under four patterns,
+    all written before any is read back, held ``hold`` x 512 clocks in between; wrong words are counted per file
+    and located to their SIMD.  No rate verdict (``ms`` is reported only).  A kernel built with a scratch segment
+    is refused by the library: it would test memory.  ``inject_block`` flips one bit of register ``inject_reg``
+    (:data:`REGFILE_REGS`) in one lane of that workgroup (self-check of the detection path; the result then carries
+    ``simd_map``, the raw rows of waves / wrong VGPR words / wrong AGPR words)."""
+    L = lib()
+    nrows = L.diag_regfile_slots()
+    errs, regs, scratch, ms = ctypes.c_ulonglong(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+    m = (ctypes.c_ulonglong * (3 * nrows))()
+    t0 = time.perf_counter()
+    _check(L.diag_regfile_test(device, rounds, seed, hold, inject_block, REGFILE_REGS.index(inject_reg),
+                               ctypes.byref(errs), m, ctypes.byref(regs), ctypes.byref(scratch), ctypes.byref(ms)))
+    rows = [r for r in range(nrows) if m[3 * r]]
+    by_file = {"vgpr": sum(m[3 * r + 1] for r in range(nrows)), "agpr": sum(m[3 * r + 2] for r in range(nrows))}
+    bad = [f"{simd_name(r)} (" + ", ".join(f"{f} {m[3 * r + c]}" for f, c in (("vgpr", 1), ("agpr", 2)) if m[3 * r + c])
+           + ")" for r in range(nrows) if m[3 * r + 1] or m[3 * r + 2]]
+    res: Dict[str, Any] = {"pass": errs.value == 0 and scratch.value == 0, "errors": errs.value, "by_file": by_file,
+                           "simds": len(rows), "waves": sum(m[3 * r] for r in rows), "regs_per_lane": regs.value,
+                           "bytes_per_simd": regs.value * 64 * 4, "scratch_bytes": scratch.value,
+                           "ms": round(ms.value, 3), "wall_s": round(time.perf_counter() - t0, 3), "detail": ""}
+    if bad:
+        res["bad_simds"] = bad
+    if errs.value:
+        res["detail"] = f"{errs.value} register words wrong on " + ", ".join(bad[:4]) + (" ..." if len(bad) > 4 else "")
+    if inject_block >= 0:
+        res["simd_map"] = list(m)
+    return res
+
+
+def valu_burn(device: int = 0, kinds=VALU_KINDS, iters: int = 2000, reps: int = 5, scale: Scale = FULL,
+              inject_block: int = -1) -> Dict[str, Any]:
+    """The vector ALU of every SIMD on the datapaths no matrix-core test reaches -- fp64 FMA, packed fp32 FMA, the
+    32-bit integer multiplier: G(FL)OP/s and wrong lanes per kind (each lane's final values must equal the host's
+    correctly rounded ones bit for bit), and where the waves ran (:func:`cu_map_summary`): the CU behind a wrong
+    result, an XCD or CU lagging the others (degraded).  Rates are judged against ``REFERENCE_RATES["valu"]`` for
+    the kinds it lists; a kind without a reference passes on rate.  ``inject_block`` (a test hook) makes one lane of
+    that workgroup wrong in the warm-up launch of every kind (the result then carries ``cu_maps``)."""
+    t0 = time.perf_counter()
+    rows: Dict[str, Any] = {}
+    rates: Dict[str, float] = {}
+    wrong = []
+    L = lib()
+    nslots = L.diag_mfma_burn_slots()
+    maps: Dict[str, Any] = {}
+    for kind in kinds:
+        rate, errs = ctypes.c_double(), ctypes.c_ulonglong()
+        m = (ctypes.c_ulonglong * (3 * nslots))()
+        _check(L.diag_valu_burn_map_x(device, VALU_KINDS.index(kind), iters, reps, inject_block, ctypes.byref(rate),
+                                      ctypes.byref(errs), m))
+        maps[kind] = list(m)
+        rows[kind] = {"gops": round(rate.value, 1), "errors": errs.value}
+        rates[kind] = rate.value
+        if errs.value:
+            wrong.append(f"{kind}: {errs.value} wrong results")
+    where = cu_map_summary(maps)
+    if where.get("bad_cus"):
+        wrong.append("on " + ", ".join(where["bad_cus"][:4]) + (" ..." if len(where["bad_cus"]) > 4 else ""))
+    ref = REFERENCE_RATES.get("valu") or {}
+    exp = {k: ref[k] * scale.compute for k in kinds if k in ref}
+    res = _rated({"kinds": rows, "map": where, "wall_s": round(time.perf_counter() - t0, 3)}, rates, exp,
+                 "GOP/s", not wrong, "; ".join(wrong))
+    if inject_block >= 0:
+        res["cu_maps"] = maps
+    return _lag_verdict(res, where, "waves")
+
+
 def l2_bandwidth(device: int = 0, slice_kib: int = 2048, passes: int = 32, blocks_per_cu: int = 8,
                  seed: int = 0x12C3, scale: Scale = FULL, inject_xcd: int = -1,
                  inject_word: int = 0) -> Dict[str, Any]:
@@ -1062,6 +1152,8 @@ LEVELS = {
     1: ("gemm_quick", "gemm_fp8_quick", "hbm_quick", "hbm_xcd", "mfma", "lds", "l2"),
     2: ("gemm", "gemm_fp8", "hbm", "hbm_xcd", "memtest", "mfma", "lds", "l2", "host_link"),
 }
+# level 3 = level 2 plus the SIMD's own parts: the vector ALU and both vector register files
+LEVELS[3] = tuple(t for t in LEVELS[2] if t != "host_link") + ("valu", "regfile", "host_link")
 
 
 def device_scale(device: int = 0, memory_partition: Optional[str] = None,
@@ -1095,6 +1187,10 @@ def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
         return lds_test(device)
     if test == "l2":
         return l2_bandwidth(device, scale=scale)
+    if test == "valu":
+        return valu_burn(device, scale=scale)
+    if test == "regfile":
+        return regfile_test(device)
     if test == "hbm_xcd":
         return hbm_xcd(device, scale=scale)
     raise ValueError(f"unknown diagnostic {test!r}")
@@ -1152,7 +1248,8 @@ def use_host_lock(lock: Any, cell: Any, label: Optional[int] = None) -> None:
 def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
         deadline: Optional[float] = None) -> Dict[str, Dict[str, Any]]:
-    """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep).
+    """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
+    the vector ALU burn-in and the register-file test).
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
     lands below the degraded line is measured once more and the better of the two is reported.  Tests of
@@ -1212,6 +1309,13 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         return f"{kinds} TFLOP/s; {m.get('cus', '?')} CUs, XCD spread {m.get('slowest_rel', 1.0):.3f}"
     if test == "lds":
         return f"{r.get('cus', '?')} CUs x {r.get('bytes_per_cu', 0) // 1024} KiB, {r.get('errors', 0)} bad words"
+    if test == "valu":
+        m = r.get("map") or {}
+        kinds = " · ".join(f"{k} {v.get('gops', 0):.0f}" for k, v in (r.get("kinds") or {}).items())
+        return f"{kinds} GOP/s; {m.get('cus', '?')} CUs, XCD spread {m.get('slowest_rel', 1.0):.3f}"
+    if test == "regfile":
+        return (f"{r.get('simds', '?')} SIMDs x {r.get('bytes_per_simd', 0) // 1024} KiB "
+                f"({r.get('regs_per_lane', '?')} registers), {r.get('errors', 0)} bad words")
     if test == "l2":
         m = r.get("map") or {}
         return f"{r.get('read_tbs', 0):.1f} TB/s, XCD spread {m.get('slowest_rel', 1.0):.3f}, {r.get('errors', 0)} bad words"
@@ -1395,7 +1499,8 @@ def main(argv=None) -> int:
     import argparse
     import json
     ap = argparse.ArgumentParser(prog="mi355x-diag", description="MI355X active diagnostics (HIP, gfx950)")
-    ap.add_argument("--level", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--level", type=int, default=1, choices=(1, 2, 3),
+                    help="1 quick, 2 deep, 3 deep plus the vector ALU and the vector register files")
     ap.add_argument("--device", type=int, action="append", help="GPU index (repeatable; default: all)")
     ap.add_argument("--parallel", type=int, default=8, help="devices tested at once (default 8; 1 = one by one)")
     ap.add_argument("--no-p2p", dest="p2p", action="store_false", help="skip the level-2 xGMI pair matrix")

@@ -50,7 +50,11 @@ class FakeDiagLib:
                  gemm_bad_tiles: Optional[Dict[Tuple[int, str], Dict[int, int]]] = None,
                  hang_devices: Tuple[int, ...] = (), abort_devices: Tuple[int, ...] = (),
                  fan_slow: Optional[Dict[Tuple[int, int], float]] = None,
-                 fan_errors: Optional[Dict[Tuple[int, int], int]] = None):
+                 fan_errors: Optional[Dict[Tuple[int, int], int]] = None,
+                 regfile_bad: Optional[Dict[Tuple[int, int], Tuple[int, int]]] = None,
+                 valu_errors: Optional[Dict[Tuple[int, int], int]] = None,
+                 valu_bad_cu: Optional[Dict[Tuple[int, int], int]] = None,
+                 valu_slow_xcd: Optional[Dict[int, float]] = None):
         from ..ops import diag
         # the fan pass (diag_p2p_fan_t): fan_slow[(src, dst)] = that pair's rate while every link of src is busy,
         # fan_errors[(src, dst)] = bad words it delivers then
@@ -95,6 +99,13 @@ class FakeDiagLib:
         self.hbm_bad = dict(hbm_bad or {})
         self.l2_bad = dict(l2_bad or {})
         self.slow_cu = dict(slow_cu or {})
+        # level 3: regfile_bad[(device, row)] = (wrong VGPR words, wrong AGPR words) on SIMD row (slot << 2 | simd);
+        # valu_errors[(device, kind)] = wrong lanes, on CU slot valu_bad_cu[(device, kind)]; valu_slow_xcd {xcd: time
+        # factor} lags the vector-ALU waves of an XCD only
+        self.regfile_bad = dict(regfile_bad or {})
+        self.valu_errors = dict(valu_errors or {})
+        self.valu_bad_cu = dict(valu_bad_cu or {})
+        self.valu_slow_xcd = dict(valu_slow_xcd or {})
         self.calls: List[str] = []
         self.threads: Dict[int, set] = {}
         self.lock = threading.Lock()
@@ -325,6 +336,58 @@ class FakeDiagLib:
         _put(errors, ctypes.c_ulonglong, total)
         _put(lds_bytes, ctypes.c_int, 163840 - 16)
         _put(ms, ctypes.c_double, 0.2)
+        return 0
+
+    def diag_regfile_slots(self):
+        return 4096
+
+    def diag_regfile_test(self, device, rounds, seed, hold, inject_block, inject_reg, errors, simd_map, regs, scratch, ms):
+        """Every SIMD of the device runs `rounds` waves; ``regfile_bad[(device, row)]`` = (VGPR, AGPR) bad words."""
+        self._log(device, "regfile")
+        if self.rc:
+            return self.rc
+        total = 0
+        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
+            for se in range(4):
+                for cu in range(8):
+                    for simd in range(4):
+                        row = (((xcd << 7) | (se << 5) | cu) << 2) | simd
+                        simd_map[3 * row] = rounds
+                        bv, ba = self.regfile_bad.get((device, row), (0, 0))
+                        if inject_block >= 0 and row == 0:
+                            bv, ba = bv + (inject_reg < 2), ba + (inject_reg >= 2)
+                        simd_map[3 * row + 1], simd_map[3 * row + 2] = bv, ba
+                        total += bv + ba
+        _put(errors, ctypes.c_ulonglong, total)
+        _put(regs, ctypes.c_int, 504)
+        _put(scratch, ctypes.c_int, 0)
+        _put(ms, ctypes.c_double, 0.3)
+        return 0
+
+    VALU_RATES = (48000.0, 105000.0, 50000.0)  # G(FL)OP/s of a kind that ops/diag.REFERENCE_RATES does not list
+
+    def diag_valu_burn_map_x(self, device, kind, iters, reps, inject_block, gops, errors, cu_map):
+        """The vector-ALU burn-in, shaped like diag_mfma_burn_map (``valu_slow_xcd``, ``valu_errors``,
+        ``valu_bad_cu``)."""
+        self._log(device, "valu")
+        if self.rc:
+            return self.rc
+        ref = (self.ref.get("valu") or {}).get(("f64", "pk_f32", "i32")[kind], self.VALU_RATES[kind])
+        _put(gops, ctypes.c_double, self.gpu_rate.get(device, self.rate) * self.compute_rate.get(device, 1.0) * ref)
+        nerr = self.valu_errors.get((device, kind), 0)
+        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
+            for se in range(4):
+                for cu in range(8):
+                    slot = (xcd << 7) | (se << 5) | cu
+                    waves = 8 * (reps + 1)
+                    cu_map[3 * slot] = waves
+                    cu_map[3 * slot + 2] = int(waves * 60000 * self.valu_slow_xcd.get(xcd, 1.0))
+        if nerr:
+            cu_map[3 * self.valu_bad_cu.get((device, kind), 0) + 1] = nerr
+        if inject_block >= 0:
+            cu_map[1] += 1
+            nerr += 1
+        _put(errors, ctypes.c_ulonglong, nerr)
         return 0
 
     def diag_host_link(self, device, nbytes, iters, h2d, d2h):

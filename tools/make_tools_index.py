@@ -13,7 +13,7 @@ GROUPS = [
                                               "copy_threshold", "scratch_ab", "rccl_rss", "contention", "final_r06",
                                               "telemetry", "sdma_")),
     ("GEMM kernels (diag.hip): A/B, labs, PMC", ("gemm_",)),
-    ("HBM / L2 / LDS / MFMA / XCD / host link", ("hbm_", "l2_", "lds_", "mall_", "mfma_", "xcd_", "hostlink",
+    ("HBM / L2 / LDS / MFMA / VALU / XCD / host link", ("hbm_", "l2_", "lds_", "mall_", "mfma_", "valu_", "xcd_", "hostlink",
                                                  "host_link", "fp8_")),
     ("Diagnostics runs and calibration", ("diag_", "cper_", "xgmi_", "explore_amdsmi")),
     ("GPU-box scripts (one gpurun call each)", ("gpu_",)),
