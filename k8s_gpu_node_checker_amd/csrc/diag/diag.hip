@@ -2135,6 +2135,46 @@ struct Timer {
     if (e1) (void)hipEventDestroy(e1);
     if (stream) (void)hipStreamDestroy(stream);
   }
+  // One timed section on stream `st`: record, `enqueue()` (queues the work; 0, or a negative code with g_err set),
+  // record, wait for it, check the last error.  0 with the section's milliseconds in *ms, else a negative code.
+  template <typename F>
+  int timed(F&& enqueue, float* ms, hipStream_t st = nullptr) {
+    DIAG_CHECK(hipEventRecord(e0, st));
+    if (const int rc = enqueue()) return rc;
+    DIAG_CHECK(hipEventRecord(e1, st));
+    DIAG_CHECK(hipEventSynchronize(e1));
+    DIAG_CHECK(hipGetLastError());
+    DIAG_CHECK(event_ms(e0, e1, ms));
+    return 0;
+  }
+};
+
+// The error counter a verifying kernel adds to and, optionally, its per-slot table (`slots` rows of `cols` counters:
+// where on the chip the waves ran and the errors were).
+struct ErrMap {
+  DevBuf cnt, tab;
+  size_t map_bytes = 0;
+  int alloc(int device, int slots, int cols, bool with_map = true) {
+    DIAG_CHECK(cnt.alloc(device, sizeof(unsigned long long)));
+    if (with_map) {
+      map_bytes = static_cast<size_t>(slots) * cols * sizeof(unsigned long long);
+      DIAG_CHECK(tab.alloc(device, map_bytes));
+    }
+    return 0;
+  }
+  unsigned long long* errors() const { return static_cast<unsigned long long*>(cnt.ptr); }
+  unsigned long long* map() const { return static_cast<unsigned long long*>(tab.ptr); }  // null without a map
+  int zero() {
+    DIAG_CHECK(hipMemset(cnt.ptr, 0, sizeof(unsigned long long)));
+    if (tab.ptr) DIAG_CHECK(hipMemset(tab.ptr, 0, map_bytes));
+    return 0;
+  }
+  // copies back the counter and the table; either destination may be null
+  int read(unsigned long long* errors_out, unsigned long long* map_out) {
+    if (errors_out) DIAG_CHECK(hipMemcpy(errors_out, cnt.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (map_out && tab.ptr) DIAG_CHECK(hipMemcpy(map_out, tab.ptr, map_bytes, hipMemcpyDeviceToHost));
+    return 0;
+  }
 };
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: it is set once for
@@ -2291,9 +2331,10 @@ int launch_bf16_ck(const void* A, const void* Bt, __bf16* C, double* csum, int M
                 : launch_v3_ck<DT_BF16>(A, Bt, C, csum, M, N, K, stream);
 }
 
-// diag_gemm_bf16_x writes bf16 C with fused column sums (else fp32 C)
-bool bf16_fused(int M, int N) {
-  const int v = bf16_variant(M, N);
+// Does the diagnostic run of `dt` (DT_BF16 / DT_FP8) at M x N write bf16 C with fused column sums (else fp32 C)?
+// The one answer for the runners, diag_gemm_ck_path and whoever calls diag_gemm_launch_ck.
+bool gemm_fused(int dt, int M, int N) {
+  const int v = dt == DT_FP8 ? fp8_variant() : bf16_variant(M, N);
   return v >= 4 || (v == 3 && v3_ck_path());
 }
 
@@ -2436,6 +2477,40 @@ inline double beyond_bf16_rounding(double got, double ref) {
   return e > 0.0 || std::isnan(e) ? e : 0.0;
 }
 
+// The `nsamp` (row, column) pairs of an M x N output that a diagnostic run checks against its reference kernel
+void sample_indices(uint64_t seed, int nsamp, int M, int N, std::vector<int>& rows, std::vector<int>& cols) {
+  rows.resize(nsamp);
+  cols.resize(nsamp);
+  uint64_t x = seed;
+  for (int i = 0; i < nsamp; ++i) {
+    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
+    rows[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(M));
+    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
+    cols[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(N));
+  }
+}
+
+// The run every burn-in shares once its tables are on the device: a checked warm-up launch (with `inject_block`,
+// the verifier's self-check), `reps` timed launches, then the wrong-lane count and (cu_map != NULL) the BURN_SLOTS
+// x 3 table over every launch.  `launch(inj, errors, map)` queues one launch of `blocks` workgroups.
+template <typename F>
+int burn_run(int device, int reps, int inject_block, F&& launch, unsigned long long* errors,
+             unsigned long long* cu_map, float* ms) {
+  ErrMap em;
+  if (em.alloc(device, BURN_SLOTS, 3, cu_map != nullptr) || em.zero()) return -1;
+  launch(inject_block < 0 ? -1 : inject_block, em.errors(), em.map());  // warm-up (also checked)
+  DIAG_CHECK(hipGetLastError());
+  DIAG_CHECK(hipDeviceSynchronize());
+  Timer tm;
+  DIAG_CHECK(tm.create());
+  const auto timed = [&] {
+    for (int r = 0; r < reps; ++r) launch(-1, em.errors(), em.map());
+    return 0;
+  };
+  if (const int rc = tm.timed(timed, ms)) return rc;
+  return em.read(errors, cu_map);
+}
+
 }  // namespace
 
 // Polled completion with a deadline (diag_p2p_copy_t): a hung copy engine or link must not block the caller.
@@ -2462,6 +2537,8 @@ hipError_t wait_event_polled(hipEvent_t ev, const PollDeadline& dl) {
 }
 }  // namespace
 
+// The agent, the tests and the tools (ops/diag.py) call each family's widest level (diag_x_x2, else diag_x_x), the
+// plain diag_x only where no test hook is passed; the wrappers under each runner keep the narrower levels exported.
 extern "C" {
 
 const char* diag_last_error(void) { return g_err.c_str(); }
@@ -2598,14 +2675,151 @@ int diag_gemm_launch_ck(int dt, const void* A, const void* Bt, void* C, double* 
 
 // 1 when diag_gemm_bf16_x (dt 0) / diag_gemm_fp8_x (dt 1) at M x N would time the bf16-output kernel with fused
 // column sums under the calling thread's knobs, 0 when it would write fp32 C
-int diag_gemm_ck_path(int dt, int M, int N) {
-  return (dt == DT_FP8 ? fp8_variant() >= 4 || v3_ck_path() : bf16_fused(M, N)) ? 1 : 0;
-}
+int diag_gemm_ck_path(int dt, int M, int N) { return gemm_fused(dt, M, N) ? 1 : 0; }
+
+}  // extern "C"
+
+namespace {
+
+// What differs between the bf16 and the fp8 diagnostic run (gemm_run): the operands and their fill, the sampled
+// reference (`Ref` values from launch_ref, each error divided by denom()), the launches, the checksums' type and tiles.
+struct GemmBf16 {
+  static constexpr int DT = DT_BF16;
+  static constexpr size_t kElemBytes = sizeof(__bf16);
+  static constexpr uint64_t kSeedA = 0x1234ULL, kSeedBt = 0xBEEFULL, kSampleSeed = 0x243F6A8885A308D3ULL;
+  using Ref = float;  // the fp32 reference kernel; an error is relative to max(1, |ref|)
+  static constexpr bool kMag = false;
+  static void fill(void* p, size_t n, uint64_t seed) {
+    hipLaunchKernelGGL(fill_bf16_kernel, dim3(2048), dim3(256), 0, nullptr, static_cast<__bf16*>(p), n, seed);
+  }
+  static void launch_ref(const void* A, const void* Bt, const int* rows, const int* cols, void* ref, void*, int nsamp,
+                         int K) {
+    hipLaunchKernelGGL(gemm_ref_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
+                       static_cast<const __bf16*>(A), static_cast<const __bf16*>(Bt), rows, cols,
+                       static_cast<float*>(ref), nsamp, K);
+  }
+  static double denom(double ref, double) { return std::max(1.0, std::fabs(ref)); }
+  static int launch_ck(const void* A, const void* Bt, __bf16* C, double* cs, int M, int N, int K) {
+    return launch_bf16_ck(A, Bt, C, cs, M, N, K, nullptr);
+  }
+  static int launch_f32(const void* A, const void* Bt, float* C, int M, int N, int K) {
+    return diag_gemm_bf16_launch(A, Bt, C, M, N, K, nullptr);
+  }
+  // the v4 / v3 kernels compute 256^2 tiles, the v1 kernel 128^2
+  static TileGeom geom(int M, int N) { return bf16_variant(M, N) == 1 ? kGeomV1 : kGeomV3; }
+};
+
+struct GemmFp8 {
+  static constexpr int DT = DT_FP8;
+  static constexpr size_t kElemBytes = 1;
+  static constexpr uint64_t kSeedA = 0x5151ULL, kSeedBt = 0xA7A7ULL, kSampleSeed = 0x13198A2E03707344ULL;
+  using Ref = double;  // the fp64 reference kernel, which also gives mag = sum|a*b|; an error is relative to mag
+  static constexpr bool kMag = true;
+  static void fill(void* p, size_t n, uint64_t seed) {
+    hipLaunchKernelGGL(fill_fp8_kernel, dim3(2048), dim3(256), 0, nullptr, static_cast<uint8_t*>(p), n, seed);
+  }
+  static void launch_ref(const void* A, const void* Bt, const int* rows, const int* cols, void* ref, void* mag,
+                         int nsamp, int K) {
+    hipLaunchKernelGGL(gemm_ref_fp8_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
+                       static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(Bt), rows, cols,
+                       static_cast<double*>(ref), static_cast<double*>(mag), nsamp, K);
+  }
+  static double denom(double, double mag) { return std::max(mag, 1e-30); }
+  static int launch_ck(const void* A, const void* Bt, __bf16* C, double* cs, int M, int N, int K) {
+    return launch_fp8_ck(A, Bt, C, cs, M, N, K / 2, nullptr);
+  }
+  static int launch_f32(const void* A, const void* Bt, float* C, int M, int N, int K) {
+    return diag_gemm_fp8_launch(A, Bt, C, M, N, K, nullptr);
+  }
+  static TileGeom geom(int, int) { return kGeomV3; }
+};
 
 // Self-contained MFMA burn-in: allocate, fill, run `iters` GEMMs, time them, verify `nsamp` sampled outputs
-// against the fp32 reference kernel and, with ck_tol >= 0, every output by tile checksums (gemm_checksum:
+// against the reference kernel and, with ck_tol >= 0, every output by tile checksums (gemm_checksum:
 // *ck_err, ck_out[kCkOut], *ck_floor).  `inject_elem` >= 0 overwrites that output between the timing and the
-// checks: with 1e6, or (inject_delta not NaN) with its own value plus inject_delta.
+// checks: with 1e6, or (inject_delta not NaN) with its own value plus inject_delta.  The shape is the caller's to check.
+template <typename T>
+int gemm_run(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+             double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
+             long long* ck_out, double* ck_floor) {
+  using Ref = typename T::Ref;
+  DIAG_CHECK(hipSetDevice(device));
+  // bf16 C and the kernel's own column sums (OUT_BF16_CK), or fp32 C
+  const bool fused = gemm_fused(T::DT, M, N);
+  DevBuf bA, bBt, bC, bcs, bref, bmag, brows, bcols, bgot;
+  DIAG_CHECK(bA.alloc(device, T::kElemBytes * static_cast<size_t>(M) * K));
+  DIAG_CHECK(bBt.alloc(device, T::kElemBytes * static_cast<size_t>(N) * K));
+  DIAG_CHECK(bC.alloc(device, (fused ? sizeof(__bf16) : sizeof(float)) * static_cast<size_t>(M) * N));
+  if (fused) DIAG_CHECK(bcs.alloc(device, sizeof(double) * static_cast<size_t>(M / 128) * N));
+  DIAG_CHECK(bref.alloc(device, sizeof(Ref) * nsamp));
+  if (T::kMag) DIAG_CHECK(bmag.alloc(device, sizeof(double) * nsamp));
+  DIAG_CHECK(brows.alloc(device, sizeof(int) * nsamp));
+  DIAG_CHECK(bcols.alloc(device, sizeof(int) * nsamp));
+  DIAG_CHECK(bgot.alloc(device, sizeof(float) * nsamp));
+  double* cs = static_cast<double*>(bcs.ptr);
+  float* C = static_cast<float*>(bC.ptr);
+  __bf16* Cb = static_cast<__bf16*>(bC.ptr);
+  const int* rows = static_cast<const int*>(brows.ptr);
+  const int* cols = static_cast<const int*>(bcols.ptr);
+  float* got = static_cast<float*>(bgot.ptr);
+  auto run = [&]() -> int {
+    return fused ? T::launch_ck(bA.ptr, bBt.ptr, Cb, cs, M, N, K) : T::launch_f32(bA.ptr, bBt.ptr, C, M, N, K);
+  };
+  T::fill(bA.ptr, static_cast<size_t>(M) * K, T::kSeedA);
+  T::fill(bBt.ptr, static_cast<size_t>(N) * K, T::kSeedBt);
+  DIAG_CHECK(hipGetLastError());
+  std::vector<int> hr, hc;
+  sample_indices(T::kSampleSeed, nsamp, M, N, hr, hc);
+  DIAG_CHECK(hipMemcpy(brows.ptr, hr.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
+  DIAG_CHECK(hipMemcpy(bcols.ptr, hc.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
+  Timer tm;
+  DIAG_CHECK(tm.create());
+  for (int i = 0; i < warmup; ++i)
+    if (run()) return -1;
+  const auto timed = [&] {
+    for (int i = 0; i < iters; ++i)
+      if (run()) return -1;
+    return 0;
+  };
+  float t_ms = 0.f;
+  if (const int rc = tm.timed(timed, &t_ms)) return rc;
+  const double ms = t_ms / std::max(iters, 1);
+  if (fused) DIAG_CHECK(inject_output_ck(Cb, cs, inject_elem, M, N, inject_delta));
+  else DIAG_CHECK(inject_output(C, inject_elem, static_cast<long long>(M) * N, inject_delta));
+  T::launch_ref(bA.ptr, bBt.ptr, rows, cols, bref.ptr, bmag.ptr, nsamp, K);
+  // gather the sampled outputs on the device: one copy instead of nsamp tiny ones
+  if (fused)
+    hipLaunchKernelGGL(gather_kernel<__bf16>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, Cb, rows, cols, got,
+                       nsamp, N);
+  else
+    hipLaunchKernelGGL(gather_kernel<float>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, C, rows, cols, got,
+                       nsamp, N);
+  DIAG_CHECK(hipGetLastError());
+  std::vector<Ref> href(nsamp);
+  std::vector<double> hmag(T::kMag ? nsamp : 0);
+  std::vector<float> hC(nsamp);
+  DIAG_CHECK(hipMemcpy(href.data(), bref.ptr, sizeof(Ref) * nsamp, hipMemcpyDeviceToHost));
+  if (T::kMag) DIAG_CHECK(hipMemcpy(hmag.data(), bmag.ptr, sizeof(double) * nsamp, hipMemcpyDeviceToHost));
+  DIAG_CHECK(hipMemcpy(hC.data(), bgot.ptr, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
+  double worst = 0.0;
+  for (int i = 0; i < nsamp; ++i) {
+    const double d = fused ? beyond_bf16_rounding(hC[i], href[i]) : std::fabs(static_cast<double>(hC[i]) - href[i]);
+    worst = std::max(worst, std::isnan(d) ? HUGE_VAL : d / T::denom(href[i], T::kMag ? hmag[i] : 0.0));
+  }
+  *max_err = worst;
+  *ms_per_iter = ms;
+  *tflops = 2.0 * M * N * static_cast<double>(K) / (ms * 1e-3) / 1e12;
+  if (ck_tol >= 0.0)
+    return gemm_checksum<T::DT>(device, bA.ptr, bBt.ptr, C, M, N, K, T::geom(M, N), ck_tol, ck_err, ck_out,
+                                fused ? cs : nullptr, ck_floor);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// bf16 GEMM burn-in (gemm_run): *max_rel_err = max |C - ref| / max(1, |ref|) over the samples.
 int diag_gemm_bf16_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
                       double inject_delta, double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter,
                       double* ck_err, long long* ck_out, double* ck_floor) {
@@ -2617,88 +2831,8 @@ int diag_gemm_bf16_x2(int device, int M, int N, int K, int warmup, int iters, in
     g_err = "gemm_bf16: M, N must be multiples of 128 and K a multiple of 64";
     return -2;
   }
-  DIAG_CHECK(hipSetDevice(device));
-  // the v4 / v3 kernels write bf16 C and their own column sums (OUT_BF16_CK); the 128^2 v1 kernel fp32 C
-  const bool fused = bf16_fused(M, N);
-  DevBuf bA, bBt, bC, bref, brows, bcols, bgot, bcs;
-  DIAG_CHECK(bA.alloc(device, sizeof(__bf16) * static_cast<size_t>(M) * K));
-  DIAG_CHECK(bBt.alloc(device, sizeof(__bf16) * static_cast<size_t>(N) * K));
-  DIAG_CHECK(bC.alloc(device, (fused ? sizeof(__bf16) : sizeof(float)) * static_cast<size_t>(M) * N));
-  if (fused) DIAG_CHECK(bcs.alloc(device, sizeof(double) * static_cast<size_t>(M / 128) * N));
-  double* cs = static_cast<double*>(bcs.ptr);
-  auto run = [&]() -> int {
-    return fused ? launch_bf16_ck(bA.ptr, bBt.ptr, static_cast<__bf16*>(bC.ptr), cs, M, N, K, nullptr)
-                 : diag_gemm_bf16_launch(bA.ptr, bBt.ptr, static_cast<float*>(bC.ptr), M, N, K, nullptr);
-  };
-  DIAG_CHECK(bref.alloc(device, sizeof(float) * nsamp));
-  DIAG_CHECK(brows.alloc(device, sizeof(int) * nsamp));
-  DIAG_CHECK(bcols.alloc(device, sizeof(int) * nsamp));
-  DIAG_CHECK(bgot.alloc(device, sizeof(float) * nsamp));
-  __bf16* A = static_cast<__bf16*>(bA.ptr);
-  __bf16* Bt = static_cast<__bf16*>(bBt.ptr);
-  float* C = static_cast<float*>(bC.ptr);
-  float* ref = static_cast<float*>(bref.ptr);
-  int* rows = static_cast<int*>(brows.ptr);
-  int* cols = static_cast<int*>(bcols.ptr);
-  hipLaunchKernelGGL(fill_bf16_kernel, dim3(2048), dim3(256), 0, nullptr, A, static_cast<size_t>(M) * K, 0x1234ULL);
-  hipLaunchKernelGGL(fill_bf16_kernel, dim3(2048), dim3(256), 0, nullptr, Bt, static_cast<size_t>(N) * K, 0xBEEFULL);
-  DIAG_CHECK(hipGetLastError());
-  std::vector<int> hr(nsamp), hc(nsamp);
-  uint64_t x = 0x243F6A8885A308D3ULL;
-  for (int i = 0; i < nsamp; ++i) {
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    hr[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(M));
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    hc[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(N));
-  }
-  DIAG_CHECK(hipMemcpy(rows, hr.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
-  DIAG_CHECK(hipMemcpy(cols, hc.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
-  Timer tm;
-  DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  for (int i = 0; i < warmup; ++i)
-    if (run()) return -1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i)
-    if (run()) return -1;
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
-  float t_ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
-  const double ms = t_ms / std::max(iters, 1);
-  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(bC.ptr), cs, inject_elem, M, N, inject_delta));
-  else DIAG_CHECK(inject_output(C, inject_elem, static_cast<long long>(M) * N, inject_delta));
-  hipLaunchKernelGGL(gemm_ref_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, A, Bt, rows, cols, ref,
-                     nsamp, K);
-  DIAG_CHECK(hipGetLastError());
-  // gather the sampled outputs on the device: one copy instead of nsamp tiny ones
-  float* got = static_cast<float*>(bgot.ptr);
-  if (fused)
-    hipLaunchKernelGGL(gather_kernel<__bf16>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
-                       static_cast<const __bf16*>(bC.ptr), rows, cols, got, nsamp, N);
-  else
-    hipLaunchKernelGGL(gather_kernel<float>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, C, rows, cols, got,
-                       nsamp, N);
-  DIAG_CHECK(hipGetLastError());
-  std::vector<float> href(nsamp), hC(nsamp);
-  DIAG_CHECK(hipMemcpy(href.data(), ref, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(hC.data(), got, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
-  double worst = 0.0;
-  for (int i = 0; i < nsamp; ++i) {
-    const double denom = std::max(1.0, std::fabs(static_cast<double>(href[i])));
-    const double d = fused ? beyond_bf16_rounding(hC[i], href[i]) : std::fabs(static_cast<double>(hC[i]) - href[i]);
-    worst = std::max(worst, std::isnan(d) ? HUGE_VAL : d / denom);
-  }
-  *max_rel_err = worst;
-  *ms_per_iter = ms;
-  *tflops = 2.0 * M * N * static_cast<double>(K) / (ms * 1e-3) / 1e12;
-  if (ck_tol >= 0.0) {
-    const int v = bf16_variant(M, N);
-    return gemm_checksum<DT_BF16>(device, A, Bt, C, M, N, K, v == 1 ? kGeomV1 : kGeomV3, ck_tol, ck_err, ck_out,
-                                  fused ? cs : nullptr, ck_floor);
-  }
-  return 0;
+  return gemm_run<GemmBf16>(device, M, N, K, warmup, iters, nsamp, inject_elem, inject_delta, ck_tol, tflops,
+                            max_rel_err, ms_per_iter, ck_err, ck_out, ck_floor);
 }
 
 // The entry point without the delta hook and the floor (the 1e6 overwrite)
@@ -2715,10 +2849,10 @@ int diag_gemm_bf16(int device, int M, int N, int K, int warmup, int iters, int n
                           nullptr, nullptr);
 }
 
-// MX-fp8 counterpart of diag_gemm_bf16_x: *max_err = max |C - ref| / sum|a*b| over the samples.
+// MX-fp8 counterpart of diag_gemm_bf16_x2: *max_err = max |C - ref| / sum|a*b| over the samples.
 int diag_gemm_fp8_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                      double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter,
-                      double* ck_err, long long* ck_out, double* ck_floor) {
+                     double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter,
+                     double* ck_err, long long* ck_out, double* ck_floor) {
   if (inject_elem >= static_cast<long long>(M) * N) {
     g_err = "gemm: inject_elem outside the output";
     return -2;
@@ -2727,84 +2861,8 @@ int diag_gemm_fp8_x2(int device, int M, int N, int K, int warmup, int iters, int
     g_err = "gemm_fp8: M, N must be multiples of 256, K a multiple of 128";
     return -2;
   }
-  DIAG_CHECK(hipSetDevice(device));
-  const bool fused = fp8_variant() >= 4 || v3_ck_path();  // bf16 C + the kernel's own column sums (OUT_BF16_CK)
-  DevBuf A, Bt, C, ref, mag, rows, cols, got, bcs;
-  DIAG_CHECK(A.alloc(device, static_cast<size_t>(M) * K));
-  DIAG_CHECK(Bt.alloc(device, static_cast<size_t>(N) * K));
-  DIAG_CHECK(C.alloc(device, (fused ? sizeof(__bf16) : sizeof(float)) * static_cast<size_t>(M) * N));
-  if (fused) DIAG_CHECK(bcs.alloc(device, sizeof(double) * static_cast<size_t>(M / 128) * N));
-  double* cs = static_cast<double*>(bcs.ptr);
-  auto run = [&]() -> int {
-    return fused ? launch_fp8_ck(A.ptr, Bt.ptr, static_cast<__bf16*>(C.ptr), cs, M, N, K / 2, nullptr)
-                 : diag_gemm_fp8_launch(A.ptr, Bt.ptr, static_cast<float*>(C.ptr), M, N, K, nullptr);
-  };
-  DIAG_CHECK(ref.alloc(device, sizeof(double) * nsamp));
-  DIAG_CHECK(mag.alloc(device, sizeof(double) * nsamp));
-  DIAG_CHECK(rows.alloc(device, sizeof(int) * nsamp));
-  DIAG_CHECK(cols.alloc(device, sizeof(int) * nsamp));
-  DIAG_CHECK(got.alloc(device, sizeof(float) * nsamp));
-  hipLaunchKernelGGL(fill_fp8_kernel, dim3(2048), dim3(256), 0, nullptr, static_cast<uint8_t*>(A.ptr),
-                     static_cast<size_t>(M) * K, 0x5151ULL);
-  hipLaunchKernelGGL(fill_fp8_kernel, dim3(2048), dim3(256), 0, nullptr, static_cast<uint8_t*>(Bt.ptr),
-                     static_cast<size_t>(N) * K, 0xA7A7ULL);
-  DIAG_CHECK(hipGetLastError());
-  std::vector<int> hr(nsamp), hc(nsamp);
-  uint64_t x = 0x13198A2E03707344ULL;
-  for (int i = 0; i < nsamp; ++i) {
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    hr[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(M));
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    hc[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(N));
-  }
-  DIAG_CHECK(hipMemcpy(rows.ptr, hr.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
-  DIAG_CHECK(hipMemcpy(cols.ptr, hc.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
-  float* c = static_cast<float*>(C.ptr);
-  for (int i = 0; i < warmup; ++i)
-    if (run()) return -1;
-  Timer tm;
-  DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i)
-    if (run()) return -1;
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
-  float t_ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
-  const double ms = t_ms / std::max(iters, 1);
-  if (fused) DIAG_CHECK(inject_output_ck(static_cast<__bf16*>(C.ptr), cs, inject_elem, M, N, inject_delta));
-  else DIAG_CHECK(inject_output(c, inject_elem, static_cast<long long>(M) * N, inject_delta));
-  const int* r = static_cast<const int*>(rows.ptr);
-  const int* cl = static_cast<const int*>(cols.ptr);
-  hipLaunchKernelGGL(gemm_ref_fp8_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
-                     static_cast<const uint8_t*>(A.ptr), static_cast<const uint8_t*>(Bt.ptr), r, cl,
-                     static_cast<double*>(ref.ptr), static_cast<double*>(mag.ptr), nsamp, K);
-  if (fused)
-    hipLaunchKernelGGL(gather_kernel<__bf16>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
-                       static_cast<const __bf16*>(C.ptr), r, cl, static_cast<float*>(got.ptr), nsamp, N);
-  else
-    hipLaunchKernelGGL(gather_kernel<float>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, c, r, cl,
-                       static_cast<float*>(got.ptr), nsamp, N);
-  DIAG_CHECK(hipGetLastError());
-  std::vector<double> href(nsamp), hmag(nsamp);
-  std::vector<float> hC(nsamp);
-  DIAG_CHECK(hipMemcpy(href.data(), ref.ptr, sizeof(double) * nsamp, hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(hmag.data(), mag.ptr, sizeof(double) * nsamp, hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(hC.data(), got.ptr, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
-  double worst = 0.0;
-  for (int i = 0; i < nsamp; ++i) {
-    const double d = fused ? beyond_bf16_rounding(hC[i], href[i]) : std::fabs(static_cast<double>(hC[i]) - href[i]);
-    worst = std::max(worst, std::isnan(d) ? HUGE_VAL : d / std::max(hmag[i], 1e-30));
-  }
-  *max_err = worst;
-  *ms_per_iter = ms;
-  *tflops = 2.0 * M * N * static_cast<double>(K) / (ms * 1e-3) / 1e12;
-  if (ck_tol >= 0.0)
-    return gemm_checksum<DT_FP8>(device, A.ptr, Bt.ptr, c, M, N, K, kGeomV3, ck_tol, ck_err, ck_out,
-                                 fused ? cs : nullptr, ck_floor);
-  return 0;
+  return gemm_run<GemmFp8>(device, M, N, K, warmup, iters, nsamp, inject_elem, inject_delta, ck_tol, tflops, max_err,
+                           ms_per_iter, ck_err, ck_out, ck_floor);
 }
 
 int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
@@ -2859,36 +2917,27 @@ int diag_hbm_bandwidth_x(int device, size_t bytes, int iters, long long inject_w
   DIAG_CHECK(hipGetLastError());
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
   const size_t nb = n * sizeof(f32x4);
-  float t_ms = 0.f;
-  // copy
-  hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, nullptr, a, b, n);
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, nullptr, a, b, n);
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
-  *copy_tbs = 2.0 * nb * iters / (t_ms * 1e-3) / 1e12;
-  // read
-  hipLaunchKernelGGL(read_kernel, dim3(grid), dim3(256), 0, nullptr, a, n, sink);
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(read_kernel, dim3(grid), dim3(256), 0, nullptr, a, n, sink);
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
-  *read_tbs = 1.0 * nb * iters / (t_ms * 1e-3) / 1e12;
+  // one phase: an untimed launch, then `iters` timed ones; the rate over `traffic` x the buffer's bytes per launch
+  auto phase = [&](auto&& launch, double traffic, double* tbs) -> int {
+    float t_ms = 0.f;
+    launch();
+    const auto loop = [&] {
+      for (int i = 0; i < iters; ++i) launch();
+      return 0;
+    };
+    if (const int rc = tm.timed(loop, &t_ms)) return rc;
+    *tbs = traffic * nb * iters / (t_ms * 1e-3) / 1e12;
+    return 0;
+  };
+  if (phase([&] { hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, nullptr, a, b, n); }, 2.0, copy_tbs))
+    return -1;
+  if (phase([&] { hipLaunchKernelGGL(read_kernel, dim3(grid), dim3(256), 0, nullptr, a, n, sink); }, 1.0, read_tbs))
+    return -1;
   if (verify(0, 1.0f)) return -1;  // b is still the copy of a (the read phase only reads a)
-  // write
-  hipLaunchKernelGGL(write_kernel, dim3(grid), dim3(256), 0, nullptr, b, n, 3.0f);
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(write_kernel, dim3(grid), dim3(256), 0, nullptr, b, n, 3.0f);
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
-  *write_tbs = 1.0 * nb * iters / (t_ms * 1e-3) / 1e12;
+  if (phase([&] { hipLaunchKernelGGL(write_kernel, dim3(grid), dim3(256), 0, nullptr, b, n, 3.0f); }, 1.0, write_tbs))
+    return -1;
   if (verify(1, 3.0f)) return -1;
-  DIAG_CHECK(hipGetLastError());
   DIAG_CHECK(hipMemcpy(errors, berr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
 }
@@ -2926,27 +2975,25 @@ int diag_memtest_x2(int device, size_t bytes, uint64_t seed, int passes, long lo
   const unsigned grid = flat_grid(n);
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int pass = 0; pass < passes; ++pass) {
-    for (int inv = 0; inv < 2; ++inv) {
-      const uint64_t s = seed + static_cast<uint64_t>(pass) * 0x9E3779B97F4A7C15ULL;
-      hipLaunchKernelGGL(mt_write_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv);
-      if (pass == inject_pass && inv == (inject_invert ? 1 : 0))
-        for (const long long w : {inject_word, inject_word2})
-          if (w >= 0) DIAG_CHECK(hipMemsetAsync(p + w, 0xA5, sizeof(uint4), nullptr));
-      hipLaunchKernelGGL(mt_verify_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv, dev, dev + 1);
+  const auto all_passes = [&]() -> int {
+    for (int pass = 0; pass < passes; ++pass) {
+      for (int inv = 0; inv < 2; ++inv) {
+        const uint64_t s = seed + static_cast<uint64_t>(pass) * 0x9E3779B97F4A7C15ULL;
+        hipLaunchKernelGGL(mt_write_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv);
+        if (pass == inject_pass && inv == (inject_invert ? 1 : 0))
+          for (const long long w : {inject_word, inject_word2})
+            if (w >= 0) DIAG_CHECK(hipMemsetAsync(p + w, 0xA5, sizeof(uint4), nullptr));
+        hipLaunchKernelGGL(mt_verify_kernel, dim3(grid), dim3(256), 0, nullptr, p, n, s, inv, dev, dev + 1);
+      }
     }
-  }
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
+    return 0;
+  };
+  float t_ms = 0.f;
+  if (const int rc = tm.timed(all_passes, &t_ms)) return rc;
   unsigned long long h[2];
   DIAG_CHECK(hipMemcpy(h, dev, sizeof h, hipMemcpyDeviceToHost));
   *errors = h[0];
   *first_bad_byte = h[0] ? h[1] * sizeof(uint4) : ~0ULL;
-  float t_ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
   *gbps = 4.0 * passes * static_cast<double>(n * sizeof(uint4)) / (t_ms * 1e-3) / 1e9;
   return 0;
 }
@@ -3232,26 +3279,12 @@ int diag_p2p_fan_t(int src, const int* dsts, int ndst, size_t bytes, int iters, 
   return 0;
 }
 
-// Matrix-core burn-in of one precision (`kind` as mfma_burn_kernel): `reps` launches of `iters`
-// iterations on every CU; *tflops = dense rate, *errors = wave-lanes whose exact result differed.
-int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
-                       unsigned long long* cu_map);
-int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* tflops,
-                         unsigned long long* errors, unsigned long long* cu_map);
-
-int diag_mfma_burn(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors) {
-  return diag_mfma_burn_map(device, kind, iters, reps, tflops, errors, nullptr);
-}
-
 int diag_mfma_burn_slots(void) { return BURN_SLOTS; }
 
-// As diag_mfma_burn, plus (cu_map != NULL) a BURN_SLOTS x 3 table of (waves, wrong lanes, wave time in
-// wall-clock ticks) per physical CU slot (wave_slot()), over every launch including the warm-up.
-int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
-                       unsigned long long* cu_map) {
-  return diag_mfma_burn_map_x(device, kind, iters, reps, -1, tflops, errors, cu_map);
-}
-
+// Matrix-core burn-in of one precision (`kind` as mfma_burn_kernel): `reps` launches of `iters`
+// iterations on every CU; *tflops = dense rate, *errors = wave-lanes whose exact result differed; (cu_map != NULL)
+// a BURN_SLOTS x 3 table of (waves, wrong lanes, wave time in wall-clock ticks) per physical CU slot (wave_slot()),
+// over every launch including the warm-up.
 // `inject_block` >= 0 (the verifier's self-check): in the warm-up launch only -- it is checked and mapped like the
 // others, and a block index lands on another CU in every launch -- lane 0 of wave 0 of that workgroup is made wrong.
 int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* tflops,
@@ -3313,31 +3346,22 @@ int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_b
     }
     expect[l] = static_cast<float>(tot * 4L * iters);  // exact: bounded below 2^24 by the check above
   }
-  DevBuf dfa, dfb, dex, dcnt, dmap;
-  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 3 * sizeof(unsigned long long);
-  if (cu_map != nullptr) {
-    DIAG_CHECK(dmap.alloc(device, map_bytes));
-    DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
-  }
+  DevBuf dfa, dfb, dex;
   DIAG_CHECK(dfa.alloc(device, fa.size()));
   DIAG_CHECK(dfb.alloc(device, fb.size()));
   DIAG_CHECK(dex.alloc(device, expect.size() * sizeof(float)));
-  DIAG_CHECK(dcnt.alloc(device, sizeof(unsigned long long)));
   DIAG_CHECK(hipMemcpy(dfa.ptr, fa.data(), fa.size(), hipMemcpyHostToDevice));
   DIAG_CHECK(hipMemcpy(dfb.ptr, fb.data(), fb.size(), hipMemcpyHostToDevice));
   DIAG_CHECK(hipMemcpy(dex.ptr, expect.data(), expect.size() * sizeof(float), hipMemcpyHostToDevice));
-  DIAG_CHECK(hipMemset(dcnt.ptr, 0, sizeof(unsigned long long)));
   const int blocks = grid_for(device, 2);  // 8 waves per CU = 2 per SIMD
   if (inject_block >= blocks) {
     g_err = "mfma_burn: inject_block outside the grid";
     return -2;
   }
-  auto launch = [&](int inj) {
+  auto launch = [&](int inj, unsigned long long* c, unsigned long long* m) {
     const i32x8* a = static_cast<const i32x8*>(dfa.ptr);
     const i32x8* b = static_cast<const i32x8*>(dfb.ptr);
     const float* ex = static_cast<const float*>(dex.ptr);
-    unsigned long long* c = static_cast<unsigned long long*>(dcnt.ptr);
-    unsigned long long* m = static_cast<unsigned long long*>(dmap.ptr);  // null without a map
     switch (kind) {
       case 0: hipLaunchKernelGGL(mfma_burn_kernel<0>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m); break;
       case 1: hipLaunchKernelGGL(mfma_burn_kernel<1>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m); break;
@@ -3345,24 +3369,22 @@ int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_b
       default: hipLaunchKernelGGL(mfma_burn_kernel<3>, dim3(blocks), dim3(256), 0, nullptr, a, b, ex, iters, inj, c, m);
     }
   };
-  launch(inject_block < 0 ? -1 : inject_block);  // warm-up (also checked)
-  DIAG_CHECK(hipGetLastError());
-  DIAG_CHECK(hipDeviceSynchronize());
-  Timer tm;
-  DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int r = 0; r < reps; ++r) launch(-1);
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
   float ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &ms));
-  DIAG_CHECK(hipMemcpy(errors, dcnt.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (cu_map != nullptr) DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  if (const int rc = burn_run(device, reps, inject_block, launch, errors, cu_map, &ms)) return rc;
   const double flop = static_cast<double>(blocks) * 4 /*waves*/ * iters * 16 /*MFMA per iter*/ * 2.0 * 16 * 16 * K;
   *tflops = ms > 0.f ? flop * reps / (ms * 1e-3) / 1e12 : 0.0;
   return 0;
+}
+
+// without the self-check hook
+int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
+                       unsigned long long* cu_map) {
+  return diag_mfma_burn_map_x(device, kind, iters, reps, -1, tflops, errors, cu_map);
+}
+
+// and without the map
+int diag_mfma_burn(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors) {
+  return diag_mfma_burn_map(device, kind, iters, reps, tflops, errors, nullptr);
 }
 
 // LDS test over `rounds` x CUs workgroups of the largest LDS allocation a workgroup may take.
@@ -3384,29 +3406,21 @@ int diag_lds_test(int device, int rounds, uint32_t seed, int inject_block, unsig
   const uint32_t dyn = static_cast<uint32_t>(max_lds) - 16u;
   DIAG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lds_test_kernel),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(dyn)));
-  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 2 * sizeof(unsigned long long);
-  DevBuf derr, dmap;
-  DIAG_CHECK(derr.alloc(device, sizeof(unsigned long long)));
-  DIAG_CHECK(dmap.alloc(device, map_bytes));
-  DIAG_CHECK(hipMemset(derr.ptr, 0, sizeof(unsigned long long)));
-  DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  ErrMap em;
+  if (em.alloc(device, BURN_SLOTS, 2) || em.zero()) return -1;
   const int blocks = grid_for(device, rounds);
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  hipLaunchKernelGGL(lds_test_kernel, dim3(blocks), dim3(1024), dyn, nullptr, dyn / 4u, seed, inject_block,
-                     static_cast<unsigned long long*>(derr.ptr), static_cast<unsigned long long*>(dmap.ptr));
-  DIAG_CHECK(hipGetLastError());
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
   float t_ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
+  const auto launch = [&] {
+    hipLaunchKernelGGL(lds_test_kernel, dim3(blocks), dim3(1024), dyn, nullptr, dyn / 4u, seed, inject_block,
+                       em.errors(), em.map());
+    return 0;
+  };
+  if (const int rc = tm.timed(launch, &t_ms)) return rc;
   *ms = t_ms;
-  DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
   *lds_bytes = static_cast<int>(dyn);
-  return 0;
+  return em.read(errors, cu_map);
 }
 
 // Register-file test over `rounds` x CUs workgroups of four 512-register waves (one per SIMD of a CU), each word held
@@ -3444,27 +3458,19 @@ int diag_regfile_test(int device, int rounds, uint32_t seed, int hold, int injec
     g_err = "regfile_test: inject_block outside the grid";
     return -2;
   }
-  const size_t map_bytes = static_cast<size_t>(RF_SLOTS) * 3 * sizeof(unsigned long long);
-  DevBuf derr, dmap;
-  DIAG_CHECK(derr.alloc(device, sizeof(unsigned long long)));
-  DIAG_CHECK(dmap.alloc(device, map_bytes));
-  DIAG_CHECK(hipMemset(derr.ptr, 0, sizeof(unsigned long long)));
-  DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  ErrMap em;
+  if (em.alloc(device, RF_SLOTS, 3) || em.zero()) return -1;
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  hipLaunchKernelGGL(regfile_test_kernel, dim3(blocks), dim3(256), 0, nullptr, seed, hold, inject_block, inject_reg,
-                     static_cast<unsigned long long*>(derr.ptr), static_cast<unsigned long long*>(dmap.ptr));
-  DIAG_CHECK(hipGetLastError());
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
   float t_ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &t_ms));
+  const auto launch = [&] {
+    hipLaunchKernelGGL(regfile_test_kernel, dim3(blocks), dim3(256), 0, nullptr, seed, hold, inject_block,
+                       inject_reg, em.errors(), em.map());
+    return 0;
+  };
+  if (const int rc = tm.timed(launch, &t_ms)) return rc;
   *ms = t_ms;
-  DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(simd_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return em.read(errors, simd_map);
 }
 
 // Vector-ALU burn-in of one kind (0 f64, 1 pk_f32, 2 i32; valu_burn_kernel): `reps` timed launches of `iters`
@@ -3487,44 +3493,22 @@ int diag_valu_burn_map_x(int device, int kind, int iters, int reps, int inject_b
   // per lane (the same in every wave, so every wave has the same answer)
   std::vector<uint64_t> ops(3 * VALU_LANES * VALU_CHAINS), expect(VALU_LANES * VALU_CHAINS);
   valu_tables(kind, static_cast<long>(iters) * VALU_UNROLL, ops.data(), expect.data());
-  DevBuf dops, dex, dcnt, dmap;
-  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 3 * sizeof(unsigned long long);
-  if (cu_map != nullptr) {
-    DIAG_CHECK(dmap.alloc(device, map_bytes));
-    DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
-  }
+  DevBuf dops, dex;
   DIAG_CHECK(dops.alloc(device, ops.size() * 8));
   DIAG_CHECK(dex.alloc(device, expect.size() * 8));
-  DIAG_CHECK(dcnt.alloc(device, sizeof(unsigned long long)));
   DIAG_CHECK(hipMemcpy(dops.ptr, ops.data(), ops.size() * 8, hipMemcpyHostToDevice));
   DIAG_CHECK(hipMemcpy(dex.ptr, expect.data(), expect.size() * 8, hipMemcpyHostToDevice));
-  DIAG_CHECK(hipMemset(dcnt.ptr, 0, sizeof(unsigned long long)));
-  auto launch = [&](int inj) {
+  auto launch = [&](int inj, unsigned long long* c, unsigned long long* m) {
     const uint64_t* o = static_cast<const uint64_t*>(dops.ptr);
     const uint64_t* ex = static_cast<const uint64_t*>(dex.ptr);
-    unsigned long long* c = static_cast<unsigned long long*>(dcnt.ptr);
-    unsigned long long* m = static_cast<unsigned long long*>(dmap.ptr);  // null without a map
     switch (kind) {
       case 0: hipLaunchKernelGGL(valu_burn_kernel<0>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m); break;
       case 1: hipLaunchKernelGGL(valu_burn_kernel<1>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m); break;
       default: hipLaunchKernelGGL(valu_burn_kernel<2>, dim3(blocks), dim3(256), 0, nullptr, o, ex, iters, inj, c, m);
     }
   };
-  launch(inject_block < 0 ? -1 : inject_block);  // warm-up (also checked)
-  DIAG_CHECK(hipGetLastError());
-  DIAG_CHECK(hipDeviceSynchronize());
-  Timer tm;
-  DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  for (int r = 0; r < reps; ++r) launch(-1);
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
   float ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &ms));
-  DIAG_CHECK(hipMemcpy(errors, dcnt.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (cu_map != nullptr) DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  if (const int rc = burn_run(device, reps, inject_block, launch, errors, cu_map, &ms)) return rc;
   const double per_step = kind == 1 ? 4.0 : 2.0;  // a float2 FMA is two FMAs
   const double op = static_cast<double>(blocks) * 256 * iters * VALU_UNROLL * VALU_CHAINS * per_step;
   *gops = ms > 0.f ? op * reps / (ms * 1e-3) / 1e9 : 0.0;
@@ -3544,37 +3528,28 @@ int diag_l2_bandwidth_x(int device, size_t slice_bytes, int passes, int blocks_p
   DIAG_CHECK(hipSetDevice(device));
   const uint32_t slice_vec = static_cast<uint32_t>(slice_bytes / 16);
   const uint32_t n_vec = 8u * slice_vec;  // XCC_ID is 0..7
-  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 3 * sizeof(unsigned long long);
-  DevBuf dbuf, derr, dmap;
+  DevBuf dbuf;
+  ErrMap em;
   DIAG_CHECK(dbuf.alloc(device, static_cast<size_t>(n_vec) * 16));
-  DIAG_CHECK(derr.alloc(device, sizeof(unsigned long long)));
-  DIAG_CHECK(dmap.alloc(device, map_bytes));
+  if (em.alloc(device, BURN_SLOTS, 3)) return -1;
   hipLaunchKernelGGL(l2_fill_kernel, dim3(1024), dim3(256), 0, nullptr, static_cast<uint4*>(dbuf.ptr), n_vec, seed);
   DIAG_CHECK(hipGetLastError());
   if (const int rc = flip_slice_word(dbuf.ptr, slice_vec, inject_xcd, inject_word, "l2_bandwidth")) return rc;
   const int blocks = grid_for(device, blocks_per_cu);
-  auto launch = [&]() {
+  const auto launch = [&] {
     hipLaunchKernelGGL(l2_read_kernel, dim3(blocks), dim3(256), 0, nullptr, static_cast<const uint4*>(dbuf.ptr),
-                       slice_vec, passes, seed, static_cast<unsigned long long*>(derr.ptr),
-                       static_cast<unsigned long long*>(dmap.ptr));
+                       slice_vec, passes, seed, em.errors(), em.map());
+    return 0;
   };
-  launch();  // untimed: brings every slice into its XCD's L2
+  launch();  // untimed: brings every slice into its XCD's L2 (its counts are cleared below)
   DIAG_CHECK(hipGetLastError());
   DIAG_CHECK(hipDeviceSynchronize());
-  DIAG_CHECK(hipMemset(derr.ptr, 0, sizeof(unsigned long long)));
-  DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  if (em.zero()) return -1;
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  DIAG_CHECK(hipEventRecord(e0, nullptr));
-  launch();
-  DIAG_CHECK(hipEventRecord(e1, nullptr));
-  DIAG_CHECK(hipEventSynchronize(e1));
-  DIAG_CHECK(hipGetLastError());
   float ms = 0.f;
-  DIAG_CHECK(event_ms(e0, e1, &ms));
-  DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  if (const int rc = tm.timed(launch, &ms)) return rc;
+  if (em.read(errors, cu_map)) return -1;
   const double bytes = static_cast<double>(blocks) * passes * static_cast<double>(slice_bytes);
   *tbs = ms > 0.f ? bytes / (ms * 1e-3) / 1e12 : 0.0;
   return 0;
@@ -3602,12 +3577,11 @@ int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu
   DIAG_CHECK(hipSetDevice(device));
   const uint32_t slice_vec = static_cast<uint32_t>(slice_bytes / 16);
   const uint32_t n_vec = 8u * slice_vec;  // XCC_ID is 0..7; 8 x 512 MiB keeps word indices in 32 bits
-  const size_t map_bytes = static_cast<size_t>(BURN_SLOTS) * 3 * sizeof(unsigned long long);
-  DevBuf dbuf, dnext, derr, dmap;
+  DevBuf dbuf, dnext;
+  ErrMap em;
   DIAG_CHECK(dbuf.alloc(device, static_cast<size_t>(n_vec) * 16));
   DIAG_CHECK(dnext.alloc(device, 8 * sizeof(unsigned int)));
-  DIAG_CHECK(derr.alloc(device, sizeof(unsigned long long)));
-  DIAG_CHECK(dmap.alloc(device, map_bytes));
+  if (em.alloc(device, BURN_SLOTS, 3)) return -1;
   hipLaunchKernelGGL(l2_fill_kernel, dim3(4096), dim3(256), 0, nullptr, static_cast<uint4*>(dbuf.ptr), n_vec, seed);
   DIAG_CHECK(hipGetLastError());
   if (const int rc = flip_slice_word(dbuf.ptr, slice_vec, inject_xcd, inject_word, "hbm_xcd")) return rc;
@@ -3619,23 +3593,22 @@ int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu
     if (hipMemset(dnext.ptr, 0, 8 * sizeof(unsigned int)) != hipSuccess) return -1.f;
     if (hipEventRecord(tm.e0, nullptr) != hipSuccess) return -1.f;
     hipLaunchKernelGGL(hbm_xcd_kernel, dim3(blocks), dim3(256), 0, nullptr, static_cast<const uint4*>(dbuf.ptr),
-                       slice_vec, passes, seed, only_xcd, static_cast<unsigned int*>(dnext.ptr),
-                       static_cast<unsigned long long*>(derr.ptr), static_cast<unsigned long long*>(dmap.ptr));
+                       slice_vec, passes, seed, only_xcd, static_cast<unsigned int*>(dnext.ptr), em.errors(),
+                       em.map());
     if (hipGetLastError() != hipSuccess || hipEventRecord(tm.e1, nullptr) != hipSuccess ||
         hipEventSynchronize(tm.e1) != hipSuccess)
       return -1.f;
     return elapsed_ms(tm.e0, tm.e1);
   };
   if (timed(-1) < 0.f) DIAG_CHECK(hipGetLastError());  // untimed warm-up: page tables, clocks up
-  DIAG_CHECK(hipMemset(derr.ptr, 0, sizeof(unsigned long long)));
-  DIAG_CHECK(hipMemset(dmap.ptr, 0, map_bytes));
+  if (em.zero()) return -1;
   const float ms = timed(-1);
   if (ms < 0.f) {
     DIAG_CHECK(hipGetLastError());
     g_err = "hbm_xcd: timed run failed";
     return -1;
   }
-  DIAG_CHECK(hipMemcpy(cu_map, dmap.ptr, map_bytes, hipMemcpyDeviceToHost));
+  if (em.read(nullptr, cu_map)) return -1;  // the timed full-chip run's map; the count goes on through the lone runs
   // bytes actually read: every XCD that has CUs reads its slice `passes` times
   bool present[8] = {false, false, false, false, false, false, false, false};
   int xcds_seen = 0;
@@ -3665,8 +3638,7 @@ int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu
       xcd_tbs[x] = xms > 0.f ? passes * static_cast<double>(slice_bytes) / (xms * 1e-3) / 1e12 : 0.0;
     }
   }
-  DIAG_CHECK(hipMemcpy(errors, derr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return 0;
+  return em.read(errors, nullptr);
 }
 
 int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
@@ -3695,20 +3667,18 @@ int diag_host_link(int device, size_t bytes, int iters, double* h2d_gbps, double
   // queue the runtime creates holds ~170 MiB of host memory for the rest of the process (tools/hip_rss_probe.hip)
   Timer tm;
   DIAG_CHECK(tm.create());
-  hipEvent_t e0 = tm.e0, e1 = tm.e1;
-  hipStream_t st = nullptr;
   for (int dir = 0; dir < 2; ++dir) {
     auto copy = [&]() {
-      return dir == 0 ? hipMemcpyAsync(dev.ptr, host, bytes, hipMemcpyHostToDevice, st)
-                      : hipMemcpyAsync(host, dev.ptr, bytes, hipMemcpyDeviceToHost, st);
+      return dir == 0 ? hipMemcpyAsync(dev.ptr, host, bytes, hipMemcpyHostToDevice, nullptr)
+                      : hipMemcpyAsync(host, dev.ptr, bytes, hipMemcpyDeviceToHost, nullptr);
     };
     DIAG_CHECK(copy());  // warm-up
-    DIAG_CHECK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) DIAG_CHECK(copy());
-    DIAG_CHECK(hipEventRecord(e1, st));
-    DIAG_CHECK(hipEventSynchronize(e1));
+    const auto copies = [&]() -> int {
+      for (int i = 0; i < iters; ++i) DIAG_CHECK(copy());
+      return 0;
+    };
     float ms = 0.f;
-    DIAG_CHECK(event_ms(e0, e1, &ms));
+    if (const int rc = tm.timed(copies, &ms)) return rc;
     const double gbps = ms > 0.f ? static_cast<double>(iters) * static_cast<double>(bytes) / (ms * 1e-3) / 1e9 : 0.0;
     *(dir == 0 ? h2d_gbps : d2h_gbps) = gbps;
   }

@@ -227,3 +227,29 @@ def test_gemm_checksums_catch_an_error_of_twice_their_floor(dev, kind, n, tile, 
     xcd = _tile_xcd(row // tile, col // tile, n // tile, n // tile, group_m)
     assert r["checksum_bad_xcds"] == {str(xcd): 1}, r
     assert "fail their checksums" in r["detail"], r
+
+
+@pytest.mark.parametrize("kind,limit_key,limit", [("gemm", "max_rel_err", "GEMM_MAX_REL_ERR"),
+                                                  ("gemm_fp8", "max_err_over_mag", "GEMM_FP8_MAX_ERR")])
+def test_gemm_fp32_output_path_checks_and_locates_an_overwritten_output(dev, kind, limit_key, limit):
+    """The v3 kernel with direct stores writes fp32 C and no column sums of its own: the runner then checks the
+    sampled outputs as they are and forms the tile checksums from C (256^2 tiles, groups of 4).  Clean, nothing
+    is flagged; one output overwritten away from the origin fails exactly its tile, charged to the XCD that
+    computed it.  The thread's knobs are back afterwards."""
+    from k8s_gpu_node_checker_amd.ops import diag
+    from test_gpu import _tile_xcd
+    fn, n, tile = getattr(diag, kind), 2048, 256
+    before = diag.get_gemm_config()
+    with diag.gemm_config(variant="v3", epilogue=False):
+        ok = fn(0, size=n, warmup=1, iters=2, samples=512)
+        row, col = n // 2 + 297, n // 3 + 501
+        r = fn(0, size=n, warmup=1, iters=2, samples=512, inject_elem=row * n + col)
+    assert diag.get_gemm_config() == before, (diag.get_gemm_config(), before)
+    print(f"{kind} {n}^3 v3 direct stores: {ok}")
+    assert ok["output"] == "fp32" and r["output"] == "fp32", (ok, r)
+    assert ok[limit_key] <= getattr(diag, limit) and ok["numerics"] == "", ok
+    assert ok["checksum_bad_tiles"] == 0, ok
+    assert r["checksum_bad_tiles"] == 1 and not r["pass"], r
+    assert r["checksum_first_bad_tile"] == [row // tile, col // tile], r
+    xcd = _tile_xcd(row // tile, col // tile, n // tile, n // tile, 4)
+    assert r["checksum_bad_xcds"] == {str(xcd): 1}, r
