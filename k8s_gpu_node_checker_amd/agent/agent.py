@@ -33,7 +33,7 @@ probing, and a GPU fault that aborts the HIP runtime costs one child.  ``thread`
 Multi-device nodes (8 GPUs, or 64 CPX partitions): per-device diagnostic jobs, at most ``--diag-parallel`` at
 once, tests of shared host resources serialized across them (``ops/diag.SHARED_TESTS``); the RCCL suite aborts its
 own communicators at its deadline (``csrc/fabric/fabric.hip``) and the xGMI copies are polled against theirs
-(``diag_p2p_copy_t``, ``diag_p2p_fan_t``).  With thread isolation a hung diagnostic cannot be ended: one that
+(``diag_p2p_copy``, ``diag_p2p_fan``).  With thread isolation a hung diagnostic cannot be ended: one that
 outlives twice its watchdog fails ``/healthz`` (fresh process), and a node-level test given up at its deadline is not
 run again in the same process (:func:`fabric_abandoned`).
 """

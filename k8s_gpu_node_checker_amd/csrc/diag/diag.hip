@@ -1748,7 +1748,7 @@ __global__ void __launch_bounds__(256) mfma_burn_kernel(const i32x8* __restrict_
   }
   const floatx4 s = acc0 + acc1 + acc2 + acc3;
   float sum = s[0] + s[1] + s[2] + s[3];
-  // the self-check of the verifier (diag_mfma_burn_map_x): one lane of one workgroup is made wrong by one, which
+  // the self-check of the verifier (diag_mfma_burn): one lane of one workgroup is made wrong by one, which
   // is exact below 2^24 and so always differs
   if (static_cast<int>(blockIdx.x) == inject_block && threadIdx.x == 0) sum += 1.0f;
   const bool bad = sum != expect[lane];
@@ -1966,7 +1966,7 @@ __global__ void __launch_bounds__(256) valu_burn_kernel(const uint64_t* __restri
 #pragma unroll
   for (int c = 0; c < VALU_CHAINS; ++c) {
     uint64_t got = ch[c].bits();
-    // the self-check of the verifier (diag_valu_burn_map_x): one bit of one chain of one lane is flipped
+    // the self-check of the verifier (diag_valu_burn): one bit of one chain of one lane is flipped
     if (c == 0 && static_cast<int>(blockIdx.x) == inject_block && threadIdx.x == 0) got ^= 1ULL;
     bad |= got != expect[lane * VALU_CHAINS + c];
   }
@@ -2513,7 +2513,7 @@ int burn_run(int device, int reps, int inject_block, F&& launch, unsigned long l
 
 }  // namespace
 
-// Polled completion with a deadline (diag_p2p_copy_t): a hung copy engine or link must not block the caller.
+// Polled completion with a deadline (diag_p2p_copy): a hung copy engine or link must not block the caller.
 namespace {
 using SteadyClock = std::chrono::steady_clock;
 struct PollDeadline {
@@ -2537,8 +2537,8 @@ hipError_t wait_event_polled(hipEvent_t ev, const PollDeadline& dl) {
 }
 }  // namespace
 
-// The agent, the tests and the tools (ops/diag.py) call each family's widest level (diag_x_x2, else diag_x_x), the
-// plain diag_x only where no test hook is passed; the wrappers under each runner keep the narrower levels exported.
+// One entry point per diagnostic: the test hooks and optional outputs are parameters of it, and each comment below
+// says which argument values mean "no hook" and which out-pointers may be null.
 extern "C" {
 
 const char* diag_last_error(void) { return g_err.c_str(); }
@@ -2673,7 +2673,7 @@ int diag_gemm_launch_ck(int dt, const void* A, const void* Bt, void* C, double* 
   return 0;
 }
 
-// 1 when diag_gemm_bf16_x (dt 0) / diag_gemm_fp8_x (dt 1) at M x N would time the bf16-output kernel with fused
+// 1 when diag_gemm_bf16 (dt 0) / diag_gemm_fp8 (dt 1) at M x N would time the bf16-output kernel with fused
 // column sums under the calling thread's knobs, 0 when it would write fp32 C
 int diag_gemm_ck_path(int dt, int M, int N) { return gemm_fused(dt, M, N) ? 1 : 0; }
 
@@ -2819,10 +2819,12 @@ int gemm_run(int device, int M, int N, int K, int warmup, int iters, int nsamp, 
 
 extern "C" {
 
-// bf16 GEMM burn-in (gemm_run): *max_rel_err = max |C - ref| / max(1, |ref|) over the samples.
-int diag_gemm_bf16_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                      double inject_delta, double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter,
-                      double* ck_err, long long* ck_out, double* ck_floor) {
+// bf16 GEMM burn-in (gemm_run): *max_rel_err = max |C - ref| / max(1, |ref|) over the samples.  No hook:
+// inject_elem = -1 (inject_delta is then unused; NaN = the 1e6 overwrite).  ck_tol < 0: no checksums, and ck_err,
+// ck_out and ck_floor may be null; with checksums ck_floor may still be null.
+int diag_gemm_bf16(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                   double inject_delta, double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter,
+                   double* ck_err, long long* ck_out, double* ck_floor) {
   if (inject_elem >= static_cast<long long>(M) * N) {
     g_err = "gemm: inject_elem outside the output";
     return -2;
@@ -2835,24 +2837,11 @@ int diag_gemm_bf16_x2(int device, int M, int N, int K, int warmup, int iters, in
                             max_rel_err, ms_per_iter, ck_err, ck_out, ck_floor);
 }
 
-// The entry point without the delta hook and the floor (the 1e6 overwrite)
-int diag_gemm_bf16_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                     double ck_tol, double* tflops, double* max_rel_err, double* ms_per_iter, double* ck_err,
-                     long long* ck_out) {
-  return diag_gemm_bf16_x2(device, M, N, K, warmup, iters, nsamp, inject_elem, std::nan(""), ck_tol, tflops,
-                           max_rel_err, ms_per_iter, ck_err, ck_out, nullptr);
-}
-
-int diag_gemm_bf16(int device, int M, int N, int K, int warmup, int iters, int nsamp, double* tflops,
-                   double* max_rel_err, double* ms_per_iter) {
-  return diag_gemm_bf16_x(device, M, N, K, warmup, iters, nsamp, -1, -1.0, tflops, max_rel_err, ms_per_iter,
-                          nullptr, nullptr);
-}
-
-// MX-fp8 counterpart of diag_gemm_bf16_x2: *max_err = max |C - ref| / sum|a*b| over the samples.
-int diag_gemm_fp8_x2(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                     double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter,
-                     double* ck_err, long long* ck_out, double* ck_floor) {
+// MX-fp8 counterpart of diag_gemm_bf16 (the same hooks; ck_floor, and without checksums ck_err and ck_out, may be
+// null): *max_err = max |C - ref| / sum|a*b| over the samples.
+int diag_gemm_fp8(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+                  double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter,
+                  double* ck_err, long long* ck_out, double* ck_floor) {
   if (inject_elem >= static_cast<long long>(M) * N) {
     g_err = "gemm: inject_elem outside the output";
     return -2;
@@ -2865,26 +2854,13 @@ int diag_gemm_fp8_x2(int device, int M, int N, int K, int warmup, int iters, int
                            ms_per_iter, ck_err, ck_out, ck_floor);
 }
 
-int diag_gemm_fp8_x(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-                    double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
-                    long long* ck_out) {
-  return diag_gemm_fp8_x2(device, M, N, K, warmup, iters, nsamp, inject_elem, std::nan(""), ck_tol, tflops, max_err,
-                          ms_per_iter, ck_err, ck_out, nullptr);
-}
-
-int diag_gemm_fp8(int device, int M, int N, int K, int warmup, int iters, int nsamp, double* tflops,
-                  double* max_err, double* ms_per_iter) {
-  return diag_gemm_fp8_x(device, M, N, K, warmup, iters, nsamp, -1, -1.0, tflops, max_err, ms_per_iter, nullptr,
-                         nullptr);
-}
-
 // HBM streams over `bytes` per buffer: copy (read+write), read-only, write-only, in TB/s.  The bytes the rates are
 // computed from are checked outside the timed loops (stream_verify_kernel): after the copy phase every 16-byte
 // element of the destination holds the source's fill, after the write phase the written value; *errors = elements
 // that did not.  `inject_word` >= 0 (the verifier's self-check) overwrites that element of the destination from the
-// host before the verification of `inject_phase` (0 = the copy's, 1 = the write's).
-int diag_hbm_bandwidth_x(int device, size_t bytes, int iters, long long inject_word, int inject_phase,
-                         double* copy_tbs, double* read_tbs, double* write_tbs, unsigned long long* errors) {
+// host before the verification of `inject_phase` (0 = the copy's, 1 = the write's); -1 = no hook.
+int diag_hbm_bandwidth(int device, size_t bytes, int iters, long long inject_word, int inject_phase,
+                       double* copy_tbs, double* read_tbs, double* write_tbs, unsigned long long* errors) {
   DIAG_CHECK(hipSetDevice(device));
   const size_t n = bytes / sizeof(f32x4);
   if (inject_word >= 0 && (static_cast<size_t>(inject_word) >= n || inject_phase < 0 || inject_phase > 1)) {
@@ -2942,18 +2918,14 @@ int diag_hbm_bandwidth_x(int device, size_t bytes, int iters, long long inject_w
   return 0;
 }
 
-int diag_hbm_bandwidth(int device, size_t bytes, int iters, double* copy_tbs, double* read_tbs, double* write_tbs) {
-  unsigned long long errors = 0;
-  return diag_hbm_bandwidth_x(device, bytes, iters, -1, 0, copy_tbs, read_tbs, write_tbs, &errors);
-}
-
 // Pattern test over `bytes` of HBM; `passes` x (pattern, inverted pattern).
 // `inject_word` >= 0: that 16-byte word is overwritten (0xA5 bytes) between one write and its verify -- the write
 // of pass `inject_pass`, its inverted half when `inject_invert` -- the fault-injection check that a corrupted word
 // is counted and located (diag.memtest(inject_word=...)); `inject_word2` >= 0 is a second word of the same write.
-int diag_memtest_x2(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
-                    long long inject_word2, int inject_pass, int inject_invert, unsigned long long* errors,
-                    unsigned long long* first_bad_byte, double* gbps) {
+// No hook: inject_word = inject_word2 = -1 (inject_pass and inject_invert are then unused).
+int diag_memtest(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
+                 long long inject_word2, int inject_pass, int inject_invert, unsigned long long* errors,
+                 unsigned long long* first_bad_byte, double* gbps) {
   DIAG_CHECK(hipSetDevice(device));
   for (const long long w : {inject_word, inject_word2})
     if (w >= 0 && static_cast<size_t>(w) >= bytes / sizeof(uint4)) {
@@ -2998,16 +2970,6 @@ int diag_memtest_x2(int device, size_t bytes, uint64_t seed, int passes, long lo
   return 0;
 }
 
-int diag_memtest_x(int device, size_t bytes, uint64_t seed, int passes, long long inject_word,
-                   unsigned long long* errors, unsigned long long* first_bad_byte, double* gbps) {
-  return diag_memtest_x2(device, bytes, seed, passes, inject_word, -1, 0, 0, errors, first_bad_byte, gbps);
-}
-
-int diag_memtest(int device, size_t bytes, uint64_t seed, int passes, unsigned long long* errors,
-                 unsigned long long* first_bad_byte, double* gbps) {
-  return diag_memtest_x(device, bytes, seed, passes, -1, errors, first_bad_byte, gbps);
-}
-
 // xGMI point-to-point check between two GPUs of the node: `iters` copies of `bytes` from `src` to
 // `dst` (hipMemcpyPeerAsync on a src-device stream, peer access enabled both ways when the pair
 // supports it -- on an MI355X hive every pair is one xGMI hop), timed with events; the received
@@ -3019,9 +2981,9 @@ int diag_memtest(int device, size_t bytes, uint64_t seed, int passes, unsigned l
 // waited on, and a pair that has not finished by then returns -4 ("hung") instead of blocking the agent's
 // node-level thread forever on a link that stopped making progress.  On that path the buffers, events and
 // stream are deliberately leaked: freeing memory an in-flight copy still targets would block (hipFree
-// synchronises the device) or let the engine write into a reused allocation.
-int diag_p2p_copy_t(int src, int dst, size_t bytes, int iters, double timeout_ms, double* gbps,
-                    unsigned long long* errors, int* peer) {
+// synchronises the device) or let the engine write into a reused allocation.  timeout_ms = 0: a blocking wait.
+int diag_p2p_copy(int src, int dst, size_t bytes, int iters, double timeout_ms, double* gbps,
+                  unsigned long long* errors, int* peer) {
   int n = 0;
   DIAG_CHECK(hipGetDeviceCount(&n));
   if (src < 0 || dst < 0 || src >= n || dst >= n || src == dst || iters < 1 || bytes < 16) {
@@ -3107,7 +3069,7 @@ int diag_p2p_copy_t(int src, int dst, size_t bytes, int iters, double timeout_ms
 // full-buffer writes of 1 GiB (finite work, ~0.15 ms each on MI355X) on a stream of their own, wait for them
 // with a `deadline_ms` deadline -- *timed_out = 1 when the deadline passed first, *waited_ms how long that
 // took -- then drain the stream (*drained_ms) before freeing, so nothing is left running.  The hung-pair path
-// of diag_p2p_copy_t cannot be provoked on a healthy node; this shows the same wait returning at its deadline.
+// of diag_p2p_copy cannot be provoked on a healthy node; this shows the same wait returning at its deadline.
 int diag_poll_selftest(int device, int launches, double deadline_ms, int* timed_out, double* waited_ms,
                        double* drained_ms) {
   if (launches < 1 || launches > 100000 || deadline_ms <= 0.0) {
@@ -3140,10 +3102,6 @@ int diag_poll_selftest(int device, int launches, double deadline_ms, int* timed_
   return 0;
 }
 
-int diag_p2p_copy(int src, int dst, size_t bytes, int iters, double* gbps, unsigned long long* errors, int* peer) {
-  return diag_p2p_copy_t(src, dst, bytes, iters, 0.0, gbps, errors, peer);
-}
-
 // The "fan" pass of the xGMI check: `src` copies to all `ndst` peers at once, so every one of its links carries
 // traffic together (the pair pass loads one link at a time; a link that holds up alone but not under load -- a
 // marginal lane retraining, an engine shared with another link -- only shows here).  One source buffer with the
@@ -3151,9 +3109,10 @@ int diag_p2p_copy(int src, int dst, size_t bytes, int iters, double* gbps, unsig
 // waits on a common start event, runs `iters` hipMemcpyPeerAsync of `bytes` and records its own end, so
 // gbps[i] = the rate peer i saw while all were running and *total_gbps = all bytes over the slowest stream's end.
 // Each destination is then verified against the pattern (errors[i]); peer[i] = direct peer access both ways.
-// `timeout_ms` > 0 bounds copies and verification as in diag_p2p_copy_t (-4 "hung", resources leaked on purpose).
-int diag_p2p_fan_t(int src, const int* dsts, int ndst, size_t bytes, int iters, double timeout_ms, double* gbps,
-                   unsigned long long* errors, int* peer, double* total_gbps) {
+// `timeout_ms` > 0 bounds copies and verification as in diag_p2p_copy (-4 "hung", resources leaked on purpose); 0 =
+// a blocking wait.
+int diag_p2p_fan(int src, const int* dsts, int ndst, size_t bytes, int iters, double timeout_ms, double* gbps,
+                 unsigned long long* errors, int* peer, double* total_gbps) {
   constexpr int kMaxFan = 64;  // a CPX hive: 63 peers
   int n = 0;
   DIAG_CHECK(hipGetDeviceCount(&n));
@@ -3286,9 +3245,10 @@ int diag_mfma_burn_slots(void) { return BURN_SLOTS; }
 // a BURN_SLOTS x 3 table of (waves, wrong lanes, wave time in wall-clock ticks) per physical CU slot (wave_slot()),
 // over every launch including the warm-up.
 // `inject_block` >= 0 (the verifier's self-check): in the warm-up launch only -- it is checked and mapped like the
-// others, and a block index lands on another CU in every launch -- lane 0 of wave 0 of that workgroup is made wrong.
-int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* tflops,
-                         unsigned long long* errors, unsigned long long* cu_map) {
+// others, and a block index lands on another CU in every launch -- lane 0 of wave 0 of that workgroup is made wrong;
+// -1 = no hook.  cu_map may be null (no map wanted).
+int diag_mfma_burn(int device, int kind, int iters, int reps, int inject_block, double* tflops,
+                   unsigned long long* errors, unsigned long long* cu_map) {
   if (kind < 0 || kind > 3 || iters < 1 || iters > 65536 || reps < 1) {
     g_err = "mfma_burn: kind 0..3, 1 <= iters <= 65536, reps >= 1";
     return -2;
@@ -3374,17 +3334,6 @@ int diag_mfma_burn_map_x(int device, int kind, int iters, int reps, int inject_b
   const double flop = static_cast<double>(blocks) * 4 /*waves*/ * iters * 16 /*MFMA per iter*/ * 2.0 * 16 * 16 * K;
   *tflops = ms > 0.f ? flop * reps / (ms * 1e-3) / 1e12 : 0.0;
   return 0;
-}
-
-// without the self-check hook
-int diag_mfma_burn_map(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors,
-                       unsigned long long* cu_map) {
-  return diag_mfma_burn_map_x(device, kind, iters, reps, -1, tflops, errors, cu_map);
-}
-
-// and without the map
-int diag_mfma_burn(int device, int kind, int iters, int reps, double* tflops, unsigned long long* errors) {
-  return diag_mfma_burn_map(device, kind, iters, reps, tflops, errors, nullptr);
 }
 
 // LDS test over `rounds` x CUs workgroups of the largest LDS allocation a workgroup may take.
@@ -3475,11 +3424,11 @@ int diag_regfile_test(int device, int rounds, uint32_t seed, int hold, int injec
 
 // Vector-ALU burn-in of one kind (0 f64, 1 pk_f32, 2 i32; valu_burn_kernel): `reps` timed launches of `iters`
 // iterations on every CU after a checked warm-up; *gops = G(FL)OP/s (an FMA or a multiply-add counts 2 per element),
-// *errors = lanes whose final values differ from the host's in any bit; cu_map as diag_mfma_burn_map's (BURN_SLOTS
+// *errors = lanes whose final values differ from the host's in any bit; cu_map as diag_mfma_burn's (BURN_SLOTS
 // x 3).  `inject_block` >= 0 (the verifier's self-check): lane 0 of wave 0 of that workgroup is made wrong in the
-// warm-up launch.
-int diag_valu_burn_map_x(int device, int kind, int iters, int reps, int inject_block, double* gops,
-                         unsigned long long* errors, unsigned long long* cu_map) {
+// warm-up launch; -1 = no hook.
+int diag_valu_burn(int device, int kind, int iters, int reps, int inject_block, double* gops,
+                   unsigned long long* errors, unsigned long long* cu_map) {
   if (kind < 0 || kind >= VALU_KINDS || iters < 1 || iters > 65536 || reps < 1) {
     g_err = "valu_burn: kind 0..2, 1 <= iters <= 65536, reps >= 1";
     return -2;
@@ -3517,9 +3466,9 @@ int diag_valu_burn_map_x(int device, int kind, int iters, int reps, int inject_b
 
 // L2 read bandwidth per XCD: 8 slices of `slice_bytes` (one per XCD id), `passes` reads of its slice by
 // every workgroup, `blocks_per_cu` workgroups of 4 waves per CU.  *tbs = aggregate bytes read / timed launch; cu_map as
-// diag_mfma_burn_map's (BURN_SLOTS x 3).  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word.
-int diag_l2_bandwidth_x(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
-                        long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map) {
+// diag_mfma_burn's (BURN_SLOTS x 3).  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word; -1 = no hook.
+int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
+                      long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map) {
   if (slice_bytes < 4096 || slice_bytes > (64u << 20) || slice_bytes % 16 || passes < 1 || passes > 1024 ||
       blocks_per_cu < 1 || blocks_per_cu > 8) {
     g_err = "l2_bandwidth: 4 KiB <= slice_bytes <= 64 MiB (multiple of 16), 1 <= passes <= 1024, 1..8 blocks/CU";
@@ -3555,19 +3504,14 @@ int diag_l2_bandwidth_x(int device, size_t slice_bytes, int passes, int blocks_p
   return 0;
 }
 
-int diag_l2_bandwidth(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
-                      unsigned long long* errors, unsigned long long* cu_map) {
-  return diag_l2_bandwidth_x(device, slice_bytes, passes, blocks_per_cu, seed, -1, 0, tbs, errors, cu_map);
-}
-
 // HBM per XCD (hbm_xcd_kernel): `slice_bytes` per XCD (8 slices, a multiple of 128 KiB, at most 512 MiB),
 // read `passes` times by the XCD's own workgroups, all XCDs at once: aggregate read TB/s, wrong words,
 // per-CU map.  With `xcd_tbs` (8 doubles) each XCD then streams its slice alone: its own read TB/s (0 for an
 // XCD without CUs on this device).  *errors counts the timed full-chip run and the lone runs; cu_map is the timed
-// full-chip run's.  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word.
-int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
-                   long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map,
-                   double* xcd_tbs) {
+// full-chip run's.  `inject_xcd` >= 0 (the verifier's self-check): flip_slice_word; -1 = no hook.  xcd_tbs may be null.
+int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, int inject_xcd,
+                 long long inject_word, double* tbs, unsigned long long* errors, unsigned long long* cu_map,
+                 double* xcd_tbs) {
   const size_t chunk = static_cast<size_t>(HBM_XCD_CHUNK_VEC) * 16;
   if (slice_bytes < chunk || slice_bytes > (512u << 20) || slice_bytes % chunk || passes < 1 || passes > 64 ||
       blocks_per_cu < 1 || blocks_per_cu > 8) {
@@ -3639,11 +3583,6 @@ int diag_hbm_xcd_x(int device, size_t slice_bytes, int passes, int blocks_per_cu
     }
   }
   return em.read(errors, nullptr);
-}
-
-int diag_hbm_xcd(int device, size_t slice_bytes, int passes, int blocks_per_cu, uint32_t seed, double* tbs,
-                 unsigned long long* errors, unsigned long long* cu_map, double* xcd_tbs) {
-  return diag_hbm_xcd_x(device, slice_bytes, passes, blocks_per_cu, seed, -1, 0, tbs, errors, cu_map, xcd_tbs);
 }
 
 // Host link check: pinned host <-> device copies of `bytes`, `iters` each way (SDMA over PCIe),

@@ -293,98 +293,54 @@ def judge_absolute(res: Dict[str, Any]) -> Dict[str, Any]:
 _lib: Optional[ctypes.CDLL] = None
 
 
+def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
+    """Every export of csrc/diag/diag.hip that this module calls: name -> (argtypes, restype); None leaves ctypes'
+    default (no declared arguments / an int result).  tests/test_native_loads.py holds it against the C source."""
+    I, Z, D, LL, V = ctypes.c_int, ctypes.c_size_t, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p
+    U32, U64 = ctypes.c_uint32, ctypes.c_uint64
+    pI, pD, pLL, pU = (ctypes.POINTER(t) for t in (I, D, LL, ctypes.c_ulonglong))
+    launch = [V, V, V, I, I, I, V]
+    gemm = [I] * 7 + [LL, D, D] + [pD] * 4 + [pLL, pD]
+    burn = [I] * 5 + [pD, pU, pU]
+    l2 = [I, Z, I, I, U32, I, LL, pD, pU, pU]
+    sig: Dict[str, Tuple[Optional[list], Any]] = {
+        "diag_last_error": (None, ctypes.c_char_p),
+        "diag_device_count": (None, I), "diag_device_arch": ([I, ctypes.c_char_p, I], None),
+        "diag_gemm_bf16_launch": (launch, None), "diag_gemm_fp8_launch": (launch, None),
+        "diag_gemm_fp4_launch": (launch, None),
+        "diag_gemm_launch_ck": ([I, V, V, V, V, I, I, I, V], None), "diag_gemm_ck_path": ([I] * 3, I),
+        "diag_gemm_bf16": (gemm, None), "diag_gemm_fp8": (gemm, None),
+        "diag_hbm_bandwidth": ([I, Z, I, LL, I] + [pD] * 3 + [pU], None),
+        "diag_memtest": ([I, Z, U64, I, LL, LL, I, I, pU, pU, pD], None),
+        "diag_mfma_burn_slots": (None, I), "diag_mfma_burn": (burn, None), "diag_valu_burn": (burn, None),
+        "diag_lds_test": ([I, I, U32, I, pU, pU, pI, pD], None),
+        "diag_regfile_slots": (None, I), "diag_regfile_test": ([I, I, U32, I, I, I, pU, pU, pI, pI, pD], None),
+        "diag_l2_bandwidth": (l2, None), "diag_hbm_xcd": (l2 + [pD], None),
+        "diag_host_link": ([I, Z, I, pD, pD], None),
+        "diag_poll_selftest": ([I, I, D, pI, pD, pD], None),
+        "diag_p2p_copy": ([I, I, Z, I, D, pD, pU, pI], None),
+        "diag_p2p_fan": ([I, pI, I, Z, I, D, pD, pU, pI, pD], None),
+    }
+    for knob in ("variant", "epilogue", "buffer_loads", "schedule", "fp8_unscaled", "tail"):
+        sig[f"diag_set_gemm_{knob}"] = ([I], None)
+        sig[f"diag_get_gemm_{knob}"] = (None, I)
+    return sig
+
+
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
         L = load_cdll("libmi355x_diag.so", required=True)
         assert L is not None
-        L.diag_last_error.restype = ctypes.c_char_p
-        L.diag_set_gemm_variant.argtypes = [ctypes.c_int]
-        L.diag_set_gemm_epilogue.argtypes = [ctypes.c_int]
-        L.diag_set_gemm_buffer_loads.argtypes = [ctypes.c_int]
-        L.diag_set_gemm_schedule.argtypes = [ctypes.c_int]
-        L.diag_set_gemm_fp8_unscaled.argtypes = [ctypes.c_int]
-        L.diag_set_gemm_tail.argtypes = [ctypes.c_int]
-        L.diag_get_gemm_tail.restype = ctypes.c_int
-        for getter in ("diag_get_gemm_variant", "diag_get_gemm_epilogue", "diag_get_gemm_buffer_loads",
-                       "diag_get_gemm_schedule", "diag_get_gemm_fp8_unscaled"):
-            getattr(L, getter).restype = ctypes.c_int
-        L.diag_device_count.restype = ctypes.c_int
-        L.diag_device_arch.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        L.diag_gemm_bf16_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.diag_gemm_bf16.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)] * 3
-        L.diag_gemm_fp8.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)] * 3
-        for f in ("diag_gemm_bf16_x", "diag_gemm_fp8_x"):
-            getattr(L, f).argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong, ctypes.c_double] + \
-                [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(ctypes.c_longlong)]
-        for f in ("diag_gemm_bf16_x2", "diag_gemm_fp8_x2"):
-            getattr(L, f).argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong, ctypes.c_double, ctypes.c_double] + \
-                [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(ctypes.c_longlong),
-                                                         ctypes.POINTER(ctypes.c_double)]
-        L.diag_gemm_fp4_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.diag_gemm_fp8_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.diag_gemm_ck_path.argtypes = [ctypes.c_int] * 3
-        L.diag_gemm_ck_path.restype = ctypes.c_int
-        L.diag_gemm_launch_ck.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.diag_hbm_bandwidth.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int] + \
-            [ctypes.POINTER(ctypes.c_double)] * 3
-        L.diag_hbm_bandwidth_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong,
-                                           ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 3 + \
-            [ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_memtest.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int,
-                                   ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
-                                   ctypes.POINTER(ctypes.c_double)]
-        L.diag_mfma_burn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_mfma_burn_map.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
-                                         ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_mfma_burn_map_x.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_double),
-                                                                ctypes.POINTER(ctypes.c_ulonglong),
-                                                                ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_mfma_burn_slots.restype = ctypes.c_int
-        L.diag_l2_bandwidth.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
-                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
-                                        ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_hbm_xcd.argtypes = list(L.diag_l2_bandwidth.argtypes) + [ctypes.POINTER(ctypes.c_double)]
-        L.diag_l2_bandwidth_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
-                                          ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
-                                          ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
-        L.diag_hbm_xcd_x.argtypes = list(L.diag_l2_bandwidth_x.argtypes) + [ctypes.POINTER(ctypes.c_double)]
-        L.diag_lds_test.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
-                                    ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
-                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
-        L.diag_regfile_slots.restype = ctypes.c_int
-        L.diag_regfile_test.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong),
-                                        ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int),
-                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
-        L.diag_valu_burn_map_x.argtypes = list(L.diag_mfma_burn_map_x.argtypes)
-        L.diag_host_link.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                     ctypes.POINTER(ctypes.c_double)]
-        L.diag_p2p_copy.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
-                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
-                                    ctypes.POINTER(ctypes.c_int)]
-        L.diag_memtest_x.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong,
-                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
-                                     ctypes.POINTER(ctypes.c_double)]
-        L.diag_memtest_x2.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong,
-                                      ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
-                                      ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
-                                      ctypes.POINTER(ctypes.c_double)]
-        L.diag_poll_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_int),
-                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        L.diag_p2p_copy_t.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_double,
-                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong),
-                                      ctypes.POINTER(ctypes.c_int)]
-        L.diag_p2p_fan_t.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_size_t,
-                                     ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
-                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int),
-                                     ctypes.POINTER(ctypes.c_double)]
+        # every name is looked up here, so a library built from an older tree -- one export per generation of a
+        # diagnostic, no diag_valu_burn or diag_p2p_fan -- raises AttributeError at load instead of being called
+        # with another generation's argument list
+        for name, (argtypes, restype) in _signatures().items():
+            fn = getattr(L, name)
+            if argtypes is not None:
+                fn.argtypes = argtypes
+            if restype is not None:
+                fn.restype = restype
         _lib = L
     return _lib
 
@@ -557,8 +513,8 @@ def _ref(test: str, key: Any, scale: float) -> float:
 def _checked_gemm(fn: str, device: int, size: int, warmup: int, iters: int, samples: int,
                   inject_elem: Optional[int], ck_tol: float,
                   inject_delta: Optional[float] = None) -> Tuple[float, float, float, float, List[int], float]:
-    """``fn`` is the ``_x2`` entry point: as ``_x`` plus ``inject_delta`` (NaN = the 1e6 overwrite) and the
-    checksums' absolute floor."""
+    """One call of ``fn`` (``diag_gemm_bf16`` / ``diag_gemm_fp8``): ``inject_elem`` None = no hook, ``inject_delta``
+    None = the 1e6 overwrite, ``ck_tol`` < 0 = no checksums (their three outputs stay 0)."""
     tf, err, ms, ck = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
     floor = ctypes.c_double()
     out = (ctypes.c_longlong * 12)()
@@ -597,6 +553,23 @@ def _checksum_verdict(res: Dict[str, Any], ck_err: float, out: List[int], tol: f
             f"{out[11]}; err {ck_err:.2e} > {tol:g})")
 
 
+def _gemm(fn: str, test: str, dt: int, err_key: str, err_text: str, max_err: float, ck_tol: float, device: int,
+          size: int, warmup: int, iters: int, samples: int, scale: Scale, inject_elem: Optional[int],
+          inject_delta: Optional[float]) -> Dict[str, Any]:
+    """What :func:`gemm` and :func:`gemm_fp8` share: the call, the result under ``err_key`` and the verdict."""
+    t0 = time.perf_counter()
+    tf, err, ms, ck, out, floor = _checked_gemm(fn, device, size, warmup, iters, samples, inject_elem, ck_tol,
+                                                inject_delta)
+    res = {"tflops": round(tf, 1), err_key: err, "ms_per_gemm": round(ms, 4),
+           "shape": [size, size, size], "output": _gemm_output(dt, size),
+           "wall_s": round(time.perf_counter() - t0, 3)}
+    problems = [f"{err_text} {err:.2e} > {max_err:g}"] if not err <= max_err else []
+    bad = _checksum_verdict(res, ck, out, ck_tol, floor)
+    problems += [bad] if bad else []
+    return _rated(res, {"tflops": tf}, {"tflops": _ref(test, size, scale.compute)}, "TFLOP/s",
+                  not problems, "; ".join(problems))
+
+
 def gemm(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20, samples: int = 4096,
          scale: Scale = FULL, inject_elem: Optional[int] = None,
          inject_delta: Optional[float] = None) -> Dict[str, Any]:
@@ -607,17 +580,8 @@ def gemm(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20, sa
     At 256-multiple sizes that fill the chip the timed kernel writes bf16 C -- the output hipBLASLt writes, so
     the rate compares like for like -- and forms the column sums itself, in fp64 from its fp32 accumulators
     (``gemm_launch_ck``); the sampled error is then what lies beyond the bf16 rounding of the output."""
-    t0 = time.perf_counter()
-    tf, err, ms, ck, out, floor = _checked_gemm("diag_gemm_bf16_x2", device, size, warmup, iters, samples,
-                                                inject_elem, GEMM_CK_TOL, inject_delta)
-    res = {"tflops": round(tf, 1), "max_rel_err": err, "ms_per_gemm": round(ms, 4),
-           "shape": [size, size, size], "output": _gemm_output(0, size),
-           "wall_s": round(time.perf_counter() - t0, 3)}
-    problems = [f"rel err {err:.2e} > {GEMM_MAX_REL_ERR:g}"] if not err <= GEMM_MAX_REL_ERR else []
-    bad = _checksum_verdict(res, ck, out, GEMM_CK_TOL, floor)
-    problems += [bad] if bad else []
-    return _rated(res, {"tflops": tf}, {"tflops": _ref("gemm", size, scale.compute)}, "TFLOP/s",
-                  not problems, "; ".join(problems))
+    return _gemm("diag_gemm_bf16", "gemm", 0, "max_rel_err", "rel err", GEMM_MAX_REL_ERR, GEMM_CK_TOL, device, size,
+                 warmup, iters, samples, scale, inject_elem, inject_delta)
 
 
 def gemm_fp8(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20,
@@ -625,17 +589,8 @@ def gemm_fp8(device: int = 0, size: int = 8192, warmup: int = 3, iters: int = 20
              inject_delta: Optional[float] = None) -> Dict[str, Any]:
     """MX-fp8 GEMM burn-in: rate, sampled fp64-reference error (normalised by sum|a*b|) and the tile
     checksums of every output, as ``gemm`` (bf16 C with fused column sums; the same test hooks)."""
-    t0 = time.perf_counter()
-    tf, err, ms, ck, out, floor = _checked_gemm("diag_gemm_fp8_x2", device, size, warmup, iters, samples,
-                                                inject_elem, GEMM_FP8_CK_TOL, inject_delta)
-    res = {"tflops": round(tf, 1), "max_err_over_mag": err, "ms_per_gemm": round(ms, 4),
-           "shape": [size, size, size], "output": _gemm_output(1, size),
-           "wall_s": round(time.perf_counter() - t0, 3)}
-    problems = [f"err {err:.2e} > {GEMM_FP8_MAX_ERR:g}"] if not err <= GEMM_FP8_MAX_ERR else []
-    bad = _checksum_verdict(res, ck, out, GEMM_FP8_CK_TOL, floor)
-    problems += [bad] if bad else []
-    return _rated(res, {"tflops": tf}, {"tflops": _ref("gemm_fp8", size, scale.compute)}, "TFLOP/s",
-                  not problems, "; ".join(problems))
+    return _gemm("diag_gemm_fp8", "gemm_fp8", 1, "max_err_over_mag", "err", GEMM_FP8_MAX_ERR, GEMM_FP8_CK_TOL, device,
+                 size, warmup, iters, samples, scale, inject_elem, inject_delta)
 
 
 def hbm(device: int = 0, gib: float = 4.0, iters: int = 10, scale: Scale = FULL,
@@ -646,10 +601,10 @@ def hbm(device: int = 0, gib: float = 4.0, iters: int = 10, scale: Scale = FULL,
     that element of the destination before the check of ``inject_phase`` (``"copy"`` or ``"write"``)."""
     c, r, w, errs = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_ulonglong()
     t0 = time.perf_counter()
-    _check(lib().diag_hbm_bandwidth_x(device, int(gib * (1 << 30)), iters,
-                                      -1 if inject_word is None else int(inject_word),
-                                      {"copy": 0, "write": 1}[inject_phase], ctypes.byref(c), ctypes.byref(r),
-                                      ctypes.byref(w), ctypes.byref(errs)))
+    _check(lib().diag_hbm_bandwidth(device, int(gib * (1 << 30)), iters,
+                                    -1 if inject_word is None else int(inject_word),
+                                    {"copy": 0, "write": 1}[inject_phase], ctypes.byref(c), ctypes.byref(r),
+                                    ctypes.byref(w), ctypes.byref(errs)))
     res = {"copy_tbs": round(c.value, 3), "read_tbs": round(r.value, 3), "write_tbs": round(w.value, 3),
            "errors": errs.value, "gib": gib, "wall_s": round(time.perf_counter() - t0, 3)}
     exp = {k: v * scale.memory for k, v in REFERENCE_RATES["hbm"].items()}
@@ -665,15 +620,11 @@ def memtest(device: int = 0, gib: float = 8.0, passes: int = 1, seed: int = 0x5E
     ``inject_pass``, its inverted half with ``inject_invert``; ``inject_word2`` is a second word of that write."""
     errs, first, gbps = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_double()
     t0 = time.perf_counter()
-    if inject_word is None and inject_word2 is None:
-        _check(lib().diag_memtest(device, int(gib * (1 << 30)), seed, passes, ctypes.byref(errs),
-                                  ctypes.byref(first), ctypes.byref(gbps)))
-    else:
-        _check(lib().diag_memtest_x2(device, int(gib * (1 << 30)), seed, passes,
-                                     -1 if inject_word is None else int(inject_word),
-                                     -1 if inject_word2 is None else int(inject_word2), inject_pass,
-                                     1 if inject_invert else 0, ctypes.byref(errs), ctypes.byref(first),
-                                     ctypes.byref(gbps)))
+    _check(lib().diag_memtest(device, int(gib * (1 << 30)), seed, passes,
+                              -1 if inject_word is None else int(inject_word),
+                              -1 if inject_word2 is None else int(inject_word2), inject_pass,
+                              1 if inject_invert else 0, ctypes.byref(errs), ctypes.byref(first),
+                              ctypes.byref(gbps)))
     ok = errs.value <= MEMTEST_MAX_ERRORS
     res: Dict[str, Any] = {"pass": ok, "errors": errs.value, "gib": gib, "passes": passes,
                            "gbps": round(gbps.value, 1), "wall_s": round(time.perf_counter() - t0, 3),
@@ -765,6 +716,15 @@ def mfma_burn(device: int = 0, kinds=MFMA_KINDS, iters: int = 2000, reps: int = 
     whose waves fall more than ``XCD_SLOW_RATIO`` behind the others (degraded).  ``inject_block`` (a test hook)
     makes one lane of that workgroup wrong in the warm-up launch of every kind (the result then carries
     ``cu_maps``, the raw per-slot tables by kind)."""
+    return _burn("diag_mfma_burn", MFMA_KINDS, "tflops", "TFLOP/s", REFERENCE_RATES["mfma"].__getitem__, device, kinds,
+                 iters, reps, scale, inject_block)
+
+
+def _burn(fn: str, table: Tuple[str, ...], rate_key: str, unit: str, ref: Any, device: int, kinds: Any, iters: int,
+          reps: int, scale: Scale, inject_block: int) -> Dict[str, Any]:
+    """What :func:`mfma_burn` and :func:`valu_burn` share: entry point ``fn`` once per kind (its index in ``table``),
+    each kind's rate under ``rate_key`` judged against ``ref(kind)`` (None: no reference, the kind passes on rate),
+    wrong results located by :func:`cu_map_summary`, lagging XCDs / CUs noted."""
     t0 = time.perf_counter()
     rows: Dict[str, Any] = {}
     rates: Dict[str, float] = {}
@@ -773,25 +733,21 @@ def mfma_burn(device: int = 0, kinds=MFMA_KINDS, iters: int = 2000, reps: int = 
     nslots = L.diag_mfma_burn_slots()
     maps: Dict[str, Any] = {}
     for kind in kinds:
-        tf, errs = ctypes.c_double(), ctypes.c_ulonglong()
+        rate, errs = ctypes.c_double(), ctypes.c_ulonglong()
         m = (ctypes.c_ulonglong * (3 * nslots))()
-        if inject_block < 0:
-            _check(L.diag_mfma_burn_map(device, MFMA_KINDS.index(kind), iters, reps, ctypes.byref(tf),
-                                        ctypes.byref(errs), m))
-        else:
-            _check(L.diag_mfma_burn_map_x(device, MFMA_KINDS.index(kind), iters, reps, inject_block,
-                                          ctypes.byref(tf), ctypes.byref(errs), m))
+        _check(getattr(L, fn)(device, table.index(kind), iters, reps, inject_block, ctypes.byref(rate),
+                              ctypes.byref(errs), m))
         maps[kind] = list(m)
-        rows[kind] = {"tflops": round(tf.value, 1), "errors": errs.value}
-        rates[kind] = tf.value
+        rows[kind] = {rate_key: round(rate.value, 1), "errors": errs.value}
+        rates[kind] = rate.value
         if errs.value:
             wrong.append(f"{kind}: {errs.value} wrong results")
     where = cu_map_summary(maps)
     if where.get("bad_cus"):
         wrong.append("on " + ", ".join(where["bad_cus"][:4]) + (" ..." if len(where["bad_cus"]) > 4 else ""))
-    exp = {k: REFERENCE_RATES["mfma"][k] * scale.compute for k in kinds}
+    exp = {k: r * scale.compute for k in kinds for r in (ref(k),) if r is not None}
     res = _rated({"kinds": rows, "map": where, "wall_s": round(time.perf_counter() - t0, 3)}, rates, exp,
-                 "TFLOP/s", not wrong, "; ".join(wrong))
+                 unit, not wrong, "; ".join(wrong))
     if inject_block >= 0:
         res["cu_maps"] = maps
     return _lag_verdict(res, where, "waves")
@@ -887,33 +843,23 @@ def valu_burn(device: int = 0, kinds=VALU_KINDS, iters: int = 2000, reps: int = 
     result, an XCD or CU lagging the others (degraded).  Rates are judged against ``REFERENCE_RATES["valu"]`` for
     the kinds it lists; a kind without a reference passes on rate.  ``inject_block`` (a test hook) makes one lane of
     that workgroup wrong in the warm-up launch of every kind (the result then carries ``cu_maps``)."""
-    t0 = time.perf_counter()
-    rows: Dict[str, Any] = {}
-    rates: Dict[str, float] = {}
-    wrong = []
+    return _burn("diag_valu_burn", VALU_KINDS, "gops", "GOP/s", (REFERENCE_RATES.get("valu") or {}).get, device, kinds,
+                 iters, reps, scale, inject_block)
+
+
+def _xcd_slices(fn: str, name: str, device: int, slice_bytes: int, passes: int, blocks_per_cu: int, seed: int,
+                inject_xcd: int, inject_word: int, *more: Any) -> Tuple[float, int, List[int], Dict[str, Any], str]:
+    """What :func:`l2_bandwidth` and :func:`hbm_xcd` share: the call (``more`` = further out-parameters of ``fn``) and
+    its map -- the rate, the wrong words, the raw per-slot table, its :func:`cu_map_summary` and the text that names
+    the CUs behind wrong words ("" when none)."""
     L = lib()
-    nslots = L.diag_mfma_burn_slots()
-    maps: Dict[str, Any] = {}
-    for kind in kinds:
-        rate, errs = ctypes.c_double(), ctypes.c_ulonglong()
-        m = (ctypes.c_ulonglong * (3 * nslots))()
-        _check(L.diag_valu_burn_map_x(device, VALU_KINDS.index(kind), iters, reps, inject_block, ctypes.byref(rate),
-                                      ctypes.byref(errs), m))
-        maps[kind] = list(m)
-        rows[kind] = {"gops": round(rate.value, 1), "errors": errs.value}
-        rates[kind] = rate.value
-        if errs.value:
-            wrong.append(f"{kind}: {errs.value} wrong results")
-    where = cu_map_summary(maps)
-    if where.get("bad_cus"):
-        wrong.append("on " + ", ".join(where["bad_cus"][:4]) + (" ..." if len(where["bad_cus"]) > 4 else ""))
-    ref = REFERENCE_RATES.get("valu") or {}
-    exp = {k: ref[k] * scale.compute for k in kinds if k in ref}
-    res = _rated({"kinds": rows, "map": where, "wall_s": round(time.perf_counter() - t0, 3)}, rates, exp,
-                 "GOP/s", not wrong, "; ".join(wrong))
-    if inject_block >= 0:
-        res["cu_maps"] = maps
-    return _lag_verdict(res, where, "waves")
+    tbs, errs = ctypes.c_double(), ctypes.c_ulonglong()
+    m = (ctypes.c_ulonglong * (3 * L.diag_mfma_burn_slots()))()
+    _check(getattr(L, fn)(device, slice_bytes, passes, blocks_per_cu, seed, inject_xcd, inject_word,
+                          ctypes.byref(tbs), ctypes.byref(errs), m, *more))
+    where = cu_map_summary({name: list(m)})
+    wrong = f"{errs.value} wrong words on " + ", ".join(where.get("bad_cus", [])[:4]) if errs.value else ""
+    return tbs.value, errs.value, list(m), where, wrong
 
 
 def l2_bandwidth(device: int = 0, slice_kib: int = 2048, passes: int = 32, blocks_per_cu: int = 8,
@@ -924,25 +870,14 @@ def l2_bandwidth(device: int = 0, slice_kib: int = 2048, passes: int = 32, block
     ``XCD_SLOW_RATIO``: an L2 that lost ways or a slow XCD), wrong words located to the CU.  ``inject_xcd`` /
     ``inject_word`` (a test hook) flip one bit of that 32-bit word of that XCD's slice before the first read;
     the result then carries ``cu_map``, the raw per-slot table (waves, wrong words, ticks) x slots."""
-    L = lib()
-    nslots = L.diag_mfma_burn_slots()
-    tbs, errs = ctypes.c_double(), ctypes.c_ulonglong()
-    m = (ctypes.c_ulonglong * (3 * nslots))()
     t0 = time.perf_counter()
-    if inject_xcd < 0:
-        _check(L.diag_l2_bandwidth(device, slice_kib << 10, passes, blocks_per_cu, seed, ctypes.byref(tbs),
-                                   ctypes.byref(errs), m))
-    else:
-        _check(L.diag_l2_bandwidth_x(device, slice_kib << 10, passes, blocks_per_cu, seed, inject_xcd, inject_word,
-                                     ctypes.byref(tbs), ctypes.byref(errs), m))
-    where = cu_map_summary({"l2": list(m)})
-    wrong = f"{errs.value} wrong words on " + ", ".join(where.get("bad_cus", [])[:4]) if errs.value else ""
+    tbs, errs, m, where, wrong = _xcd_slices("diag_l2_bandwidth", "l2", device, slice_kib << 10, passes, blocks_per_cu,
+                                             seed, inject_xcd, inject_word)
     exp = {"read_tbs": REFERENCE_RATES["l2"]["read_tbs"] * scale.compute}
-    res = _rated({"read_tbs": round(tbs.value, 2), "errors": errs.value, "map": where,
-                  "wall_s": round(time.perf_counter() - t0, 3)}, {"read_tbs": tbs.value}, exp, "TB/s",
-                 not errs.value, wrong)
+    res = _rated({"read_tbs": round(tbs, 2), "errors": errs, "map": where,
+                  "wall_s": round(time.perf_counter() - t0, 3)}, {"read_tbs": tbs}, exp, "TB/s", not errs, wrong)
     if inject_xcd >= 0:
-        res["cu_map"] = list(m)
+        res["cu_map"] = m
     return _lag_verdict(res, where, "L2 reads")
 
 
@@ -958,27 +893,18 @@ def hbm_xcd(device: int = 0, slice_mib: int = 256, passes: int = 4, blocks_per_c
     run of all XCDs and the lone runs; the map is the timed run's.  ``inject_xcd`` / ``inject_word`` (a test hook)
     flip one bit of that 32-bit word of that XCD's slice before the first read (the result then carries ``cu_map``,
     the raw per-slot table)."""
-    L = lib()
-    nslots = L.diag_mfma_burn_slots()
-    tbs, errs = ctypes.c_double(), ctypes.c_ulonglong()
-    m = (ctypes.c_ulonglong * (3 * nslots))()
     alone = (ctypes.c_double * 8)()
     t0 = time.perf_counter()
-    if inject_xcd < 0:
-        _check(L.diag_hbm_xcd(device, slice_mib << 20, passes, blocks_per_cu, seed, ctypes.byref(tbs),
-                              ctypes.byref(errs), m, alone))
-    else:
-        _check(L.diag_hbm_xcd_x(device, slice_mib << 20, passes, blocks_per_cu, seed, inject_xcd, inject_word,
-                                ctypes.byref(tbs), ctypes.byref(errs), m, alone))
-    where = cu_map_summary({"hbm_xcd": list(m)})
+    tbs, errs, m, where, wrong = _xcd_slices("diag_hbm_xcd", "hbm_xcd", device, slice_mib << 20, passes, blocks_per_cu,
+                                             seed, inject_xcd, inject_word, alone)
     # under contention the XCDs' shares of HBM are not even (measured 1.02-1.29x between runs): reported only
     where = {k: v for k, v in where.items() if k in ("cus", "xcds", "bad_cus")}
     per = {x: alone[x] for x in range(8) if alone[x] > 0}
-    res: Dict[str, Any] = {"read_tbs": round(tbs.value, 3), "errors": errs.value,
+    res: Dict[str, Any] = {"read_tbs": round(tbs, 3), "errors": errs,
                            "alone_tbs": {str(x): round(v, 3) for x, v in per.items()}, "map": where}
     if inject_xcd >= 0:
-        res["cu_map"] = list(m)
-    rates = {"read_tbs": tbs.value}
+        res["cu_map"] = m
+    rates = {"read_tbs": tbs}
     exp = {"read_tbs": REFERENCE_RATES["hbm_xcd"]["read_tbs"] * scale.memory}
     notes = []
     if per:
@@ -989,11 +915,10 @@ def hbm_xcd(device: int = 0, slice_mib: int = 256, passes: int = 4, blocks_per_c
         exp["slowest_xcd_tbs"] = min(REFERENCE_RATES["hbm_xcd"]["alone_tbs"], exp["read_tbs"])
         if med > 0 and per[slow] < XCD_ALONE_MIN_RATIO * med:
             notes.append(f"xcd{slow} reads HBM at {per[slow]:.2f} TB/s alone, {per[slow] / med:.2f}x the median XCD")
-    wrong = f"{errs.value} wrong words on " + ", ".join(where.get("bad_cus", [])[:4]) if errs.value else ""
     res["wall_s"] = round(time.perf_counter() - t0, 3)
     if notes:
         res["lag"] = notes
-    return _rated(res, rates, exp, "TB/s", not errs.value, wrong)
+    return _rated(res, rates, exp, "TB/s", not errs, wrong)
 
 
 def host_link(device: int = 0, mib: int = 256, iters: int = 5, scale: Scale = FULL) -> Dict[str, Any]:
@@ -1016,7 +941,7 @@ def poll_selftest(device: int = 0, launches: int = 1000, deadline_ms: float = 20
     return {"timed_out": bool(t.value), "waited_ms": round(w.value, 3), "drained_ms": round(d.value, 3)}
 
 
-P2P_HUNG = -4  # diag_p2p_copy_t: the copies (or their verification) missed the deadline
+P2P_HUNG = -4  # diag_p2p_copy / diag_p2p_fan: the copies (or their verification) missed the deadline
 
 
 def p2p_copy(src: int, dst: int, mib: int = 256, iters: int = 5, timeout_s: Optional[float] = None) -> Dict[str, Any]:
@@ -1027,8 +952,8 @@ def p2p_copy(src: int, dst: int, mib: int = 256, iters: int = 5, timeout_s: Opti
     blocking the caller on a link that stopped making progress."""
     gbps, errs, peer = ctypes.c_double(), ctypes.c_ulonglong(), ctypes.c_int()
     ms = 0.0 if not timeout_s else max(1.0, 1000.0 * timeout_s)
-    rc = lib().diag_p2p_copy_t(src, dst, mib << 20, iters, ms, ctypes.byref(gbps), ctypes.byref(errs),
-                               ctypes.byref(peer))
+    rc = lib().diag_p2p_copy(src, dst, mib << 20, iters, ms, ctypes.byref(gbps), ctypes.byref(errs),
+                             ctypes.byref(peer))
     if rc == P2P_HUNG:
         return {"src": src, "dst": dst, "gbps": 0.0, "errors": 0, "peer": bool(peer.value), "hung": True,
                 "detail": lib().diag_last_error().decode(errors="replace")}
@@ -1055,7 +980,7 @@ def p2p_fan(src: int, dsts: List[int], mib: int = 256, iters: int = 5,
     gbps, errs, peer = (ctypes.c_double * n)(), (ctypes.c_ulonglong * n)(), (ctypes.c_int * n)()
     total = ctypes.c_double()
     ms = 0.0 if not timeout_s else max(1.0, 1000.0 * timeout_s)
-    rc = lib().diag_p2p_fan_t(src, arr, n, mib << 20, iters, ms, gbps, errs, peer, ctypes.byref(total))
+    rc = lib().diag_p2p_fan(src, arr, n, mib << 20, iters, ms, gbps, errs, peer, ctypes.byref(total))
     if rc == P2P_HUNG:
         return {"src": src, "hung": True, "detail": lib().diag_last_error().decode(errors="replace"), "to": []}
     _check(rc)
@@ -1164,36 +1089,24 @@ def device_scale(device: int = 0, memory_partition: Optional[str] = None,
     return Scale.of(info.get("cus"), info.get("mem_bytes"), memory_partition, power_fraction)
 
 
+# each test of LEVELS: the function that runs it (by name: looked up per call, so a replaced function is the one
+# run) and its arguments besides the device and -- for the tests with a rate verdict -- the scale
+_QUICK = dict(size=4096, warmup=2, iters=10, samples=1024)
+_TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
+    "gemm_quick": ("gemm", _QUICK), "gemm_fp8_quick": ("gemm_fp8", _QUICK),
+    "hbm_quick": ("hbm", dict(gib=2.0, iters=5)),
+    "gemm": ("gemm", {}), "gemm_fp8": ("gemm_fp8", {}), "hbm": ("hbm", {}), "hbm_xcd": ("hbm_xcd", {}),
+    "memtest": ("memtest", {}), "mfma": ("mfma_burn", {}), "lds": ("lds_test", {}), "l2": ("l2_bandwidth", {}),
+    "valu": ("valu_burn", {}), "regfile": ("regfile_test", {}), "host_link": ("host_link", {}),
+}
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test"))  # error counts only: nothing to scale
+
+
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
-    if test == "gemm_quick":
-        return gemm(device, size=4096, warmup=2, iters=10, samples=1024, scale=scale)
-    if test == "gemm_fp8_quick":
-        return gemm_fp8(device, size=4096, warmup=2, iters=10, samples=1024, scale=scale)
-    if test == "gemm_fp8":
-        return gemm_fp8(device, scale=scale)
-    if test == "hbm_quick":
-        return hbm(device, gib=2.0, iters=5, scale=scale)
-    if test == "gemm":
-        return gemm(device, scale=scale)
-    if test == "hbm":
-        return hbm(device, scale=scale)
-    if test == "memtest":
-        return memtest(device)
-    if test == "mfma":
-        return mfma_burn(device, scale=scale)
-    if test == "host_link":
-        return host_link(device, scale=scale)
-    if test == "lds":
-        return lds_test(device)
-    if test == "l2":
-        return l2_bandwidth(device, scale=scale)
-    if test == "valu":
-        return valu_burn(device, scale=scale)
-    if test == "regfile":
-        return regfile_test(device)
-    if test == "hbm_xcd":
-        return hbm_xcd(device, scale=scale)
-    raise ValueError(f"unknown diagnostic {test!r}")
+    if test not in _TESTS:
+        raise ValueError(f"unknown diagnostic {test!r}")
+    fn, kwargs = _TESTS[test]
+    return globals()[fn](device, **kwargs, **({} if fn in _UNSCALED else {"scale": scale}))
 
 
 def _slow_only(res: Dict[str, Any]) -> bool:

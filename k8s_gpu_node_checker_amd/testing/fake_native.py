@@ -10,9 +10,25 @@ cycles; the real libraries run under ``tests/test_gpu.py`` on an MI355X.
 from __future__ import annotations
 
 import ctypes
+import inspect
 import threading
 import time
 from typing import Dict, List, Optional, Tuple
+
+
+def diag_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeDiagLib` stands in for, read from csrc/diag/diag.hip: every function defined at the
+    top level of its ``extern "C"`` blocks -> its parameter declarations (``(void)``: none).  Exports of diagnostic
+    builds only (inside an ``#ifdef``) are left out."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "diag", "diag.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(diag_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
 
 
 def _put(ptr, ctype, value) -> None:
@@ -56,7 +72,7 @@ class FakeDiagLib:
                  valu_bad_cu: Optional[Dict[Tuple[int, int], int]] = None,
                  valu_slow_xcd: Optional[Dict[int, float]] = None):
         from ..ops import diag
-        # the fan pass (diag_p2p_fan_t): fan_slow[(src, dst)] = that pair's rate while every link of src is busy,
+        # the fan pass (diag_p2p_fan): fan_slow[(src, dst)] = that pair's rate while every link of src is busy,
         # fan_errors[(src, dst)] = bad words it delivers then
         self.fan_slow = dict(fan_slow or {})
         self.fan_errors = dict(fan_errors or {})
@@ -133,6 +149,13 @@ class FakeDiagLib:
                 return self.rates.pop(0)
         return self.gpu_rate.get(device, self.rate)
 
+    def _slots(self):
+        """(xcd, slot) of every CU of the device: 8 XCDs (a partition: its share of them) x 4 SEs x 8 CUs."""
+        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
+            for se in range(4):
+                for cu in range(8):
+                    yield xcd, (xcd << 7) | (se << 5) | cu
+
     def _log(self, device: int, what: str) -> None:
         with self.lock:
             self.calls.append(what)
@@ -174,9 +197,6 @@ class FakeDiagLib:
         _put(ms, ctypes.c_double, 0.1)
         return self.rc
 
-    def diag_gemm_bf16(self, device, m, n, k, warmup, iters, samples, tflops, err, ms):
-        return self._gemm("gemm", device, m, tflops, err, ms)
-
     def _checksums(self, test, device, inject, ck_err, out):
         """Tile checksums: ``gemm_bad_tiles[(device, test)] = {xcd: tiles}``; an injected element = one bad
         tile on XCD 0, as on the GPU (workgroup 0 computes tile (0, 0) on XCD 0)."""
@@ -193,50 +213,45 @@ class FakeDiagLib:
             out[i] = v
         _put(ck_err, ctypes.c_double, 0.4 if vals[0] else 3e-8)
 
-    def diag_gemm_bf16_x(self, device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out):
-        rc = self._gemm("gemm", device, m, tflops, err, ms)
+    def _checked(self, test, device, size, inject, tol, tflops, err, ms, ck_err, out, floor):
+        rc = self._gemm(test, device, size, tflops, err, ms)
+        if floor:
+            _put(floor, ctypes.c_double, max(tol, 0.0) * 5.2e5)  # tol x the largest column sum|a*b|
         if rc == 0 and tol >= 0:
-            self._checksums("gemm", device, inject, ck_err, out)
+            self._checksums(test, device, inject, ck_err, out)
         return rc
 
-    def diag_gemm_fp8_x(self, device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out):
-        rc = self._gemm("gemm_fp8", device, m, tflops, err, ms)
-        if rc == 0 and tol >= 0:
-            self._checksums("gemm_fp8", device, inject, ck_err, out)
-        return rc
+    def diag_gemm_bf16(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err, out,
+                       floor):
+        return self._checked("gemm", device, m, inject, tol, tflops, err, ms, ck_err, out, floor)
 
-    def diag_gemm_bf16_x2(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err,
-                          out, floor):
-        _put(floor, ctypes.c_double, max(tol, 0.0) * 5.2e5)  # tol x the largest column sum|a*b|
-        return self.diag_gemm_bf16_x(device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out)
+    def diag_gemm_fp8(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err, out,
+                      floor):
+        return self._checked("gemm_fp8", device, m, inject, tol, tflops, err, ms, ck_err, out, floor)
 
-    def diag_gemm_fp8_x2(self, device, m, n, k, warmup, iters, samples, inject, delta, tol, tflops, err, ms, ck_err,
-                         out, floor):
-        _put(floor, ctypes.c_double, max(tol, 0.0) * 5.2e5)
-        return self.diag_gemm_fp8_x(device, m, n, k, warmup, iters, samples, inject, tol, tflops, err, ms, ck_err, out)
-
-    def diag_gemm_fp8(self, device, m, n, k, warmup, iters, samples, tflops, err, ms):
-        return self._gemm("gemm_fp8", device, m, tflops, err, ms)
-
-    def diag_hbm_bandwidth(self, device, nbytes, iters, c, r, w):
+    def diag_hbm_bandwidth(self, device, nbytes, iters, inject_word, inject_phase, c, r, w, errs):
         self._log(device, "hbm")
         f = self._rate(device)
+        _put(errs, ctypes.c_ulonglong, 1 if inject_word >= 0 else 0)
         _put(c, ctypes.c_double, f * self.ref["hbm"]["copy_tbs"])
         _put(r, ctypes.c_double, f * self.ref["hbm"]["read_tbs"])
         _put(w, ctypes.c_double, f * 6.9)
         return self.rc
 
-    def diag_hbm_bandwidth_x(self, device, nbytes, iters, inject_word, inject_phase, c, r, w, errs):
-        _put(errs, ctypes.c_ulonglong, 1 if inject_word >= 0 else 0)
-        return self.diag_hbm_bandwidth(device, nbytes, iters, c, r, w)
-
-    def diag_memtest(self, device, nbytes, seed, passes, errs, first, gbps):
+    def diag_memtest(self, device, nbytes, seed, passes, inject_word, inject_word2, inject_pass, inject_invert, errs,
+                     first, gbps):
         self._log(device, "memtest")
         _put(errs, ctypes.c_ulonglong, 0)
         _put(gbps, ctypes.c_double, 5400.0)
         return self.rc
 
-    def diag_mfma_burn(self, device, kind, iters, reps, tflops, errors):
+    def diag_mfma_burn_slots(self):
+        return 1024
+
+    def diag_mfma_burn(self, device, kind, iters, reps, inject_block, tflops, errors, cu_map):
+        """The rate and wrong results of one kind and, with ``cu_map``, the per-CU table: 8 XCDs x 32 CUs (4 SEs x
+        8), 8 waves per CU and launch; ``slow_xcd`` {xcd: time factor} and ``bad_cu`` {(device, kind): slot} shape
+        it."""
         self._log(device, "mfma")
         if self.rc:
             return self.rc
@@ -247,31 +262,20 @@ class FakeDiagLib:
                      * self.ref["mfma"][self.kinds[kind]], 0)
         _put(tflops, ctypes.c_double, tf)
         _put(errors, ctypes.c_ulonglong, self.mfma_errors.get((device, kind), e))
-        return 0
-
-    def diag_mfma_burn_slots(self):
-        return 1024
-
-    def diag_mfma_burn_map(self, device, kind, iters, reps, tflops, errors, cu_map):
-        """diag_mfma_burn plus the per-CU table: 8 XCDs x 32 CUs (4 SEs x 8), 8 waves per CU and
-        launch; ``slow_xcd`` {xcd: time factor} and ``bad_cu`` {(device, kind): slot} shape it."""
-        rc = self.diag_mfma_burn(device, kind, iters, reps, tflops, errors)
-        if rc or not cu_map:
-            return rc
+        if not cu_map:
+            return 0
         nerr = self.mfma_errors.get((device, kind), 0)
         bad_slot = self.bad_cu.get((device, kind))
-        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
-            for se in range(4):
-                for cu in range(8):
-                    slot = (xcd << 7) | (se << 5) | cu
-                    waves = 8 * (reps + 1)
-                    cu_map[3 * slot] = waves
-                    cu_map[3 * slot + 2] = int(waves * 40000 * self.slow_xcd.get(xcd, 1.0) * self.slow_cu.get(slot, 1.0))
+        for xcd, slot in self._slots():
+            waves = 8 * (reps + 1)
+            cu_map[3 * slot] = waves
+            cu_map[3 * slot + 2] = int(waves * 40000 * self.slow_xcd.get(xcd, 1.0) * self.slow_cu.get(slot, 1.0))
         if bad_slot is not None and nerr:
             cu_map[3 * bad_slot + 1] = nerr
         return 0
 
-    def diag_l2_bandwidth(self, device, slice_bytes, passes, blocks_per_cu, seed, tbs, errors, cu_map):
+    def diag_l2_bandwidth(self, device, slice_bytes, passes, blocks_per_cu, seed, inject_xcd, inject_word, tbs, errors,
+                          cu_map):
         """Aggregate rate = rate x reference; per-CU table shaped like the burn-in's (``slow_xcd`` applies,
         ``l2_bad[(device, slot)]`` = wrong words read there)."""
         self._log(device, "l2")
@@ -279,20 +283,18 @@ class FakeDiagLib:
             return self.rc
         _put(tbs, ctypes.c_double, self._rate(device) * self.ref["l2"]["read_tbs"])
         total = 0
-        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
-            for se in range(4):
-                for cu in range(8):
-                    slot = (xcd << 7) | (se << 5) | cu
-                    waves = 4 * blocks_per_cu
-                    cu_map[3 * slot] = waves
-                    cu_map[3 * slot + 2] = int(waves * 90000 * self.slow_xcd.get(xcd, 1.0))
-                    bad = self.l2_bad.get((device, slot), 0)
-                    cu_map[3 * slot + 1] = bad
-                    total += bad
+        for xcd, slot in self._slots():
+            waves = 4 * blocks_per_cu
+            cu_map[3 * slot] = waves
+            cu_map[3 * slot + 2] = int(waves * 90000 * self.slow_xcd.get(xcd, 1.0))
+            bad = self.l2_bad.get((device, slot), 0)
+            cu_map[3 * slot + 1] = bad
+            total += bad
         _put(errors, ctypes.c_ulonglong, total)
         return 0
 
-    def diag_hbm_xcd(self, device, slice_bytes, passes, blocks_per_cu, seed, tbs, errors, cu_map, xcd_tbs):
+    def diag_hbm_xcd(self, device, slice_bytes, passes, blocks_per_cu, seed, inject_xcd, inject_word, tbs, errors,
+                     cu_map, xcd_tbs):
         """All XCDs together at rate x reference; each XCD alone at rate x reference x ``hbm_xcd_slow``."""
         self._log(device, "hbm_xcd")
         if self.rc:
@@ -306,16 +308,13 @@ class FakeDiagLib:
             # (rate) is normalised by its CU share
             share = min(1.0, self.cus / 256)
             xcd_tbs[xcd] = r / share * 1.31 * self.hbm_xcd_slow.get(xcd, 1.0) if xcd < nx else 0.0
-        for xcd in range(nx):
-            for se in range(4):
-                for cu in range(8):
-                    slot = (xcd << 7) | (se << 5) | cu
-                    waves = 4 * blocks_per_cu
-                    cu_map[3 * slot] = waves
-                    cu_map[3 * slot + 2] = waves * 50000
-                    bad = self.hbm_bad.get((device, slot), 0)
-                    cu_map[3 * slot + 1] = bad
-                    total += bad
+        for _, slot in self._slots():
+            waves = 4 * blocks_per_cu
+            cu_map[3 * slot] = waves
+            cu_map[3 * slot + 2] = waves * 50000
+            bad = self.hbm_bad.get((device, slot), 0)
+            cu_map[3 * slot + 1] = bad
+            total += bad
         _put(errors, ctypes.c_ulonglong, total)
         return 0
 
@@ -325,14 +324,11 @@ class FakeDiagLib:
         if self.rc:
             return self.rc
         total = 0
-        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
-            for se in range(4):
-                for cu in range(8):
-                    slot = (xcd << 7) | (se << 5) | cu
-                    cu_map[2 * slot] = rounds
-                    bad = self.lds_bad.get((device, slot), 0) + (1 if inject_block >= 0 and slot == 0 else 0)
-                    cu_map[2 * slot + 1] = bad
-                    total += bad
+        for xcd, slot in self._slots():
+            cu_map[2 * slot] = rounds
+            bad = self.lds_bad.get((device, slot), 0) + (1 if inject_block >= 0 and slot == 0 else 0)
+            cu_map[2 * slot + 1] = bad
+            total += bad
         _put(errors, ctypes.c_ulonglong, total)
         _put(lds_bytes, ctypes.c_int, 163840 - 16)
         _put(ms, ctypes.c_double, 0.2)
@@ -347,17 +343,15 @@ class FakeDiagLib:
         if self.rc:
             return self.rc
         total = 0
-        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
-            for se in range(4):
-                for cu in range(8):
-                    for simd in range(4):
-                        row = (((xcd << 7) | (se << 5) | cu) << 2) | simd
-                        simd_map[3 * row] = rounds
-                        bv, ba = self.regfile_bad.get((device, row), (0, 0))
-                        if inject_block >= 0 and row == 0:
-                            bv, ba = bv + (inject_reg < 2), ba + (inject_reg >= 2)
-                        simd_map[3 * row + 1], simd_map[3 * row + 2] = bv, ba
-                        total += bv + ba
+        for _, slot in self._slots():
+            for simd in range(4):
+                row = (slot << 2) | simd
+                simd_map[3 * row] = rounds
+                bv, ba = self.regfile_bad.get((device, row), (0, 0))
+                if inject_block >= 0 and row == 0:
+                    bv, ba = bv + (inject_reg < 2), ba + (inject_reg >= 2)
+                simd_map[3 * row + 1], simd_map[3 * row + 2] = bv, ba
+                total += bv + ba
         _put(errors, ctypes.c_ulonglong, total)
         _put(regs, ctypes.c_int, 504)
         _put(scratch, ctypes.c_int, 0)
@@ -366,8 +360,8 @@ class FakeDiagLib:
 
     VALU_RATES = (48000.0, 105000.0, 50000.0)  # G(FL)OP/s of a kind that ops/diag.REFERENCE_RATES does not list
 
-    def diag_valu_burn_map_x(self, device, kind, iters, reps, inject_block, gops, errors, cu_map):
-        """The vector-ALU burn-in, shaped like diag_mfma_burn_map (``valu_slow_xcd``, ``valu_errors``,
+    def diag_valu_burn(self, device, kind, iters, reps, inject_block, gops, errors, cu_map):
+        """The vector-ALU burn-in, shaped like diag_mfma_burn (``valu_slow_xcd``, ``valu_errors``,
         ``valu_bad_cu``)."""
         self._log(device, "valu")
         if self.rc:
@@ -375,13 +369,10 @@ class FakeDiagLib:
         ref = (self.ref.get("valu") or {}).get(("f64", "pk_f32", "i32")[kind], self.VALU_RATES[kind])
         _put(gops, ctypes.c_double, self.gpu_rate.get(device, self.rate) * self.compute_rate.get(device, 1.0) * ref)
         nerr = self.valu_errors.get((device, kind), 0)
-        for xcd in range(8 if self.cus >= 256 else max(1, self.cus // 32)):
-            for se in range(4):
-                for cu in range(8):
-                    slot = (xcd << 7) | (se << 5) | cu
-                    waves = 8 * (reps + 1)
-                    cu_map[3 * slot] = waves
-                    cu_map[3 * slot + 2] = int(waves * 60000 * self.valu_slow_xcd.get(xcd, 1.0))
+        for xcd, slot in self._slots():
+            waves = 8 * (reps + 1)
+            cu_map[3 * slot] = waves
+            cu_map[3 * slot + 2] = int(waves * 60000 * self.valu_slow_xcd.get(xcd, 1.0))
         if nerr:
             cu_map[3 * self.valu_bad_cu.get((device, kind), 0) + 1] = nerr
         if inject_block >= 0:
@@ -405,10 +396,7 @@ class FakeDiagLib:
         _put(d2h, ctypes.c_double, d)
         return self.rc
 
-    def diag_p2p_copy(self, src, dst, nbytes, iters, gbps, errors, peer):
-        return self.diag_p2p_copy_t(src, dst, nbytes, iters, 0.0, gbps, errors, peer)
-
-    def diag_p2p_copy_t(self, src, dst, nbytes, iters, timeout_ms, gbps, errors, peer):
+    def diag_p2p_copy(self, src, dst, nbytes, iters, timeout_ms, gbps, errors, peer):
         with self.lock:  # node-level: runs on the agent's main thread, after the per-GPU threads
             self.calls.append(f"p2p{src}->{dst}")
             self.p2p_timeouts_ms.append(float(timeout_ms))
@@ -428,7 +416,7 @@ class FakeDiagLib:
         _put(peer, ctypes.c_int, 0 if (src, dst) in self.nopeer else 1)
         return 0
 
-    def diag_p2p_fan_t(self, src, dsts, ndst, nbytes, iters, timeout_ms, gbps, errors, peer, total):
+    def diag_p2p_fan(self, src, dsts, ndst, nbytes, iters, timeout_ms, gbps, errors, peer, total):
         """Every peer of ``src`` at once: a pair's rate is ``fan_slow[(src, dst)]`` when given (a link that holds up
         alone but not under load), else its pair rate (``slow_pairs`` / ``p2p_gbps``)."""
         with self.lock:
@@ -511,11 +499,9 @@ class NarrowedDiagLib:
     """A :class:`FakeDiagLib` as a process sees it with ``HIP_VISIBLE_DEVICES=k``: one device, ordinal 0 = GPU k
     (what a per-device diagnostic child of the agent sees, agent/isolation.narrow_to)."""
 
-    _PER_DEVICE = frozenset(("diag_device_arch", "diag_gemm_bf16", "diag_gemm_bf16_x", "diag_gemm_fp8_x",
-                             "diag_gemm_fp8", "diag_gemm_bf16_x2", "diag_gemm_fp8_x2", "diag_hbm_bandwidth",
-                             "diag_hbm_bandwidth_x", "diag_memtest", "diag_memtest_x", "diag_mfma_burn",
-                             "diag_mfma_burn_map", "diag_l2_bandwidth", "diag_hbm_xcd", "diag_lds_test",
-                             "diag_host_link", "diag_poll_selftest"))
+    # the calls whose first argument is a device ordinal (diag_p2p_* take ``src`` and the node's own ordinals)
+    _PER_DEVICE = frozenset(name for name, fn in vars(FakeDiagLib).items() if name.startswith("diag_")
+                            and list(inspect.signature(fn).parameters)[1:2] == ["device"])
 
     def __init__(self, lib: FakeDiagLib, physical: int):
         self.lib, self.physical = lib, physical

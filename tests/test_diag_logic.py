@@ -455,3 +455,55 @@ def test_fabric_tests_report_a_raising_test_as_failed(fake, monkeypatch):
     monkeypatch.setattr(diag, "p2p_matrix", bad_pair)
     out = diag.fabric_tests([0, 1], rccl=False)
     assert out["p2p"]["pass"] is False and "out of memory" in out["p2p"]["detail"] and "rccl" not in out
+
+
+# exports ops/diag.py calls that the fake deliberately lacks: the GEMM knobs and launches on caller-owned memory (the
+# "absent from the test doubles" guards and the GPU tests cover them) and the polled-wait self-test of real HIP
+NOT_FAKED = frozenset(
+    [f"diag_{op}_gemm_{k}" for op in ("set", "get")
+     for k in ("variant", "epilogue", "tail", "buffer_loads", "schedule", "fp8_unscaled")]
+    + ["diag_gemm_bf16_launch", "diag_gemm_fp8_launch", "diag_gemm_fp4_launch", "diag_gemm_launch_ck",
+       "diag_gemm_ck_path", "diag_poll_selftest"])
+
+
+def test_fake_abi_has_every_entry_point_the_front_end_calls_with_the_c_arity():
+    import inspect
+    import re
+
+    from k8s_gpu_node_checker_amd.testing.fake_native import diag_c_exports
+    with open(diag.__file__) as f:
+        source = f.read()
+    # read as attributes of lib(), or named in a string: the signature table, getattr() and the shared helpers' ``fn``
+    used = set(re.findall(r"(?:\bL|lib\(\))\.(diag_\w+)", source)) | set(re.findall(r"\"(diag_\w+)\"", source))
+    exports = diag_c_exports()
+    assert {"diag_gemm_bf16", "diag_valu_burn", "diag_p2p_fan", "diag_last_error"} <= used  # the scan finds them
+    assert used <= set(exports), used - set(exports)
+    faked = {n for n in vars(FakeDiagLib) if n.startswith("diag_")}
+    assert used - faked <= NOT_FAKED and not faked & NOT_FAKED, (used - faked - NOT_FAKED, faked & NOT_FAKED)
+    assert faked <= set(exports), faked - set(exports)  # nothing the library does not export
+    for name in sorted(faked):
+        params = list(inspect.signature(getattr(FakeDiagLib, name)).parameters.values())[1:]
+        assert all(p.kind is p.POSITIONAL_OR_KEYWORD and p.default is p.empty for p in params), name
+        assert len(params) == len(exports[name]), (name, [p.name for p in params], exports[name])
+
+
+def test_narrowed_child_reaches_its_own_gpu_in_every_per_device_call(monkeypatch):
+    """A child narrowed to GPU 2 sees it as ordinal 0 in every call that takes a device, level 3's included (the
+    per-device calls are derived from the fake's signatures); the pair calls keep the node's ordinals."""
+    from k8s_gpu_node_checker_amd.testing.fake_native import NarrowedDiagLib
+    assert {"diag_valu_burn", "diag_regfile_test", "diag_memtest", "diag_mfma_burn", "diag_l2_bandwidth",
+            "diag_hbm_xcd", "diag_device_arch"} <= NarrowedDiagLib._PER_DEVICE
+    assert not any(n.startswith("diag_p2p") or n == "diag_device_count" for n in NarrowedDiagLib._PER_DEVICE)
+    lib = NarrowedDiagLib(FakeDiagLib(n=4, valu_errors={(2, 0): 3}, regfile_bad={(2, 0): (1, 0)}), physical=2)
+    monkeypatch.setattr(diag, "lib", lambda: lib)
+    r = diag.valu_burn(0)
+    assert not r["pass"] and r["kinds"]["f64"]["errors"] == 3 and r["kinds"]["pk_f32"]["errors"] == 0, r
+    r = diag.regfile_test(0)
+    assert not r["pass"] and r["errors"] == 1 and r["by_file"] == {"vgpr": 1, "agpr": 0}, r
+    assert diag.device_count() == 1 and diag.device_info(0)["bdf"] == "0000:25:00.0"
+    import ctypes
+    out = [ctypes.c_double(), ctypes.c_ulonglong()]
+    m = (ctypes.c_ulonglong * (3 * 1024))()
+    assert lib.diag_valu_burn(1, 0, 16, 1, -1, ctypes.byref(out[0]), ctypes.byref(out[1]), m) == -1
+    with pytest.raises(RuntimeError, match="invalid device ordinal"):
+        diag.regfile_test(1)

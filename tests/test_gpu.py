@@ -545,12 +545,15 @@ def test_diag_failed_allocation_leaks_nothing(dev):
     torch.cuda.synchronize()
     free0, total = torch.cuda.mem_get_info(0)
     d = [ctypes.c_double() for _ in range(3)]
+    errs = ctypes.c_ulonglong()
     big = int(free0 * 0.7) // (1 << 20) << 20  # the first buffer fits, the second cannot
     for _ in range(3):
-        assert L.diag_hbm_bandwidth(0, big, 1, *(ctypes.byref(x) for x in d)) == -1
+        assert L.diag_hbm_bandwidth(0, big, 1, -1, 0, *(ctypes.byref(x) for x in d), ctypes.byref(errs)) == -1
         assert b"out of memory" in L.diag_last_error().lower()
         m = 393216  # C alone is 618 GB; A and Bt (805 MB each) are allocated first
-        assert L.diag_gemm_bf16(0, m, m, 1024, 0, 1, 16, *(ctypes.byref(x) for x in d)) == -1
+        # no hook, no checksums (their outputs may then be null)
+        assert L.diag_gemm_bf16(0, m, m, 1024, 0, 1, 16, -1, float("nan"), -1.0, *(ctypes.byref(x) for x in d),
+                                None, None, None) == -1
     free1, _ = torch.cuda.mem_get_info(0)
     assert free0 - free1 < (256 << 20), (free0, free1)
     r = _as_production(lambda: diag.hbm(0, gib=0.5, iters=2))  # and the next call runs clean
@@ -814,7 +817,7 @@ def test_agent_diagnostics_threads_per_device(dev):
 
 
 def test_polled_deadline_returns_at_its_deadline(dev):
-    """The wait the xGMI pair copies use (diag_p2p_copy_t) on real HIP: ~150 ms of queued work waited for with a
+    """The wait the xGMI pair copies use (diag_p2p_copy) on real HIP: ~150 ms of queued work waited for with a
     20 ms deadline comes back at the deadline, and the work then drains; with a generous deadline it completes."""
     from k8s_gpu_node_checker_amd.ops import diag
     r = diag.poll_selftest(0, launches=1000, deadline_ms=20.0)
@@ -1053,7 +1056,7 @@ def test_gemm_knobs_are_thread_local_and_concurrent_threads_agree(dev):
 
 
 def test_xgmi_fan_entry_point_on_one_gpu(dev):
-    """diag_p2p_fan_t loads and validates on real HIP (a one-GPU box has no peers to fan to): a fan to the source
+    """diag_p2p_fan loads and validates on real HIP (a one-GPU box has no peers to fan to): a fan to the source
     itself is refused before anything is allocated; the matrix skips a lone GPU."""
     from k8s_gpu_node_checker_amd.ops import diag
     with pytest.raises(RuntimeError, match="every peer must be a device other than the source"):

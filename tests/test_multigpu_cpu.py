@@ -325,7 +325,7 @@ def test_hung_collective_is_aborted_and_reported_as_a_failed_rccl_row(node8):
 
 
 def test_hung_xgmi_pair_is_given_up_at_its_share_of_the_deadline(node8):
-    """A pair whose copies never complete (diag_p2p_copy_t polls its completion event): the matrix gives up at
+    """A pair whose copies never complete (diag_p2p_copy polls its completion event): the matrix gives up at
     P2P_SHARE of the watchdog, names the pair, and the RCCL suite still runs in what is left."""
     lib, fab = node8(hung_pairs=((3, 5),))
     ag = A.Agent("n8", source="fake", diag_level=2, expect_gpus=8, diag_timeout=1.0)

@@ -136,11 +136,12 @@ int main(int argc, char** argv) {
       return 1;
     }
     step("dlopen diag library");
-    using hbm_fn = int (*)(int, size_t, int, double*, double*, double*);
+    using hbm_fn = int (*)(int, size_t, int, long long, int, double*, double*, double*, unsigned long long*);
     auto hbm = reinterpret_cast<hbm_fn>(dlsym(h, "diag_hbm_bandwidth"));
     if (hbm) {
       double c = 0, r = 0, w = 0;
-      int rc = hbm(0, size_t(256) << 20, 2, &c, &r, &w);
+      unsigned long long errors = 0;
+      int rc = hbm(0, size_t(256) << 20, 2, -1, 0, &c, &r, &w, &errors);  // -1: no self-check hook
       std::printf("{\"diag_hbm_rc\":%d,\"read_tbs\":%.3f}\n", rc, r);
       step("diag_hbm 256 MiB (first launch from the library)");
     }
