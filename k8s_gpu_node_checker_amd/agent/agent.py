@@ -404,15 +404,18 @@ def _annotation_gpu(g: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
-def _fabric_suite(devices: List[int], timeout_s: Optional[float] = None, link: Optional[float] = None) -> Dict[str, Any]:
+def _fabric_suite(devices: List[int], timeout_s: Optional[float] = None, link: Optional[float] = None,
+                  kernel: bool = False) -> Dict[str, Any]:
     """The node-level tests (``ops/diag.fabric_tests``): the xGMI pair matrix (pairs, then every source's fan to all
-    its peers; ``link`` = one link's GB/s from amd-smi's training, the absolute floor's anchor) and the RCCL
+    its peers; ``link`` = one link's GB/s from amd-smi's training, the absolute floor's anchor; ``kernel``: then the
+    kernel-driven passes, which say of a slow copy whether the link or the copy engine was slow) and the RCCL
     collectives, both under the watchdog's deadline -- the matrix within ``P2P_SHARE`` of it, the collectives
     within what is left up to 90 % -- so a hung copy or collective is given up, and named in the report,
     rather than left holding the fabric job."""
     from ..ops import diag
     try:
-        res = diag.fabric_tests(devices, timeout_s=timeout_s or None, link=link)
+        extra = {"kernel": True} if kernel else {}  # off: fabric_tests is called as it always was
+        res = diag.fabric_tests(devices, timeout_s=timeout_s or None, link=link, **extra)
     except Exception as e:  # the diag library itself is missing
         return {"p2p": {"pass": False, "detail": f"{type(e).__name__}: {e}"[:200]}}
     m, r = res.get("p2p") or {}, res.get("rccl") or {}
@@ -420,6 +423,8 @@ def _fabric_suite(devices: List[int], timeout_s: Optional[float] = None, link: O
                                                      "detail", "wall_s", "stopped") if k in m}}
     if isinstance(m.get("fan"), dict):  # the fan's summary (its per-destination rows stay with mi355x-diag)
         out["p2p"]["fan"] = {k: v for k, v in m["fan"].items() if k != "to"}
+    if isinstance(m.get("kernel"), dict):  # likewise the kernel path's: medians, minima and the rows that stand out
+        out["p2p"]["kernel"] = {k: v for k, v in m["kernel"].items() if k not in ("pairs", "fan")}
     out["rccl"] = {k: r.get(k) for k in ("pass", "best_busbw_gbps", "best_busbw_by_op", "detail", "wall_s",
                                          "rccl", "aborted") if k in r or k not in ("aborted",)}
     return out
@@ -438,8 +443,9 @@ class Agent:
                  pod_resources_socket: Optional[str] = None, gpu_resources: Sequence[str] = (PRIMARY_GPU_KEY,),
                  label_node: bool = False, annotation_encoding: str = "json", diag_parallel: int = DIAG_PARALLEL,
                  diag_baseline: bool = True, baseline_file: Optional[str] = None, isolation: str = "thread",
-                 diag_setup: Optional[tuple] = None):
+                 diag_setup: Optional[tuple] = None, diag_xgmi_kernel: bool = False):
         self.node = node
+        self.diag_xgmi_kernel = diag_xgmi_kernel  # the node-level suite also runs the kernel-driven xGMI passes
         if isolation not in ISOLATION:
             raise ValueError(f"isolation must be one of {ISOLATION}")
         # where the HIP work runs (agent/isolation.py): "process" -- disposable children of a forkserver started
@@ -787,7 +793,8 @@ class Agent:
             # trained down is judged against its hive's links, not the other way round
             links = sorted(diag.link_gbs(g.get("xgmi_width"), g.get("xgmi_speed_gbps"))
                            for g in (entries.get(d) or {} for d in devices))
-            suite = functools.partial(_fabric_suite, link=links[len(links) // 2] if links else None)
+            suite = functools.partial(_fabric_suite, link=links[len(links) // 2] if links else None,
+                                      **({"kernel": True} if self.diag_xgmi_kernel else {}))
             job = self.workers.fabric(suite, devices, self.diag_timeout, done)
             self._fabric_thread = _DiagRun(job, now, time.monotonic())
         if self._fabric_thread is not None:
@@ -1156,6 +1163,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="a process other than the agent holding this much VRAM makes its GPU busy (default 2048)")
     ap.add_argument("--diag-timeout", type=float, default=300.0,
                     help="a GPU whose diagnostics run longer than this (s) is reported failed (hung); default 300")
+    ap.add_argument("--diag-xgmi-kernel", action="store_true",
+                    help="level 2: after the xGMI copy passes, load the links from a kernel too (CU stores and loads), "
+                         "and say of every slow copy whether the link or the copy engine was slow")
     ap.add_argument("--diag-isolation", choices=ISOLATION, default="process",
                     help="process (default): each cycle's HIP diagnostics run in disposable child processes, so the "
                          "agent never initialises HIP, a hung one is SIGKILLed at --diag-timeout and a GPU fault "
@@ -1222,7 +1232,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                   gpu_resources=tuple(args.gpu_resource or (PRIMARY_GPU_KEY,)), label_node=args.label_node,
                   annotation_encoding=args.annotation_encoding, diag_parallel=args.diag_parallel,
                   diag_baseline=args.diag_baseline, baseline_file=args.diag_baseline_file,
-                  isolation=args.diag_isolation)
+                  isolation=args.diag_isolation, diag_xgmi_kernel=args.diag_xgmi_kernel)
     if args.diag_baseline_reset and agent.baselines is not None:
         spec = args.diag_baseline_reset.strip()
         gone = agent.baselines.drop(None if spec.lower() == "all" else spec.split(","))

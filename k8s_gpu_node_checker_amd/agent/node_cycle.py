@@ -20,7 +20,7 @@ from typing import Any, Dict, List, Optional
 
 
 def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: int = 8,
-        fabric: bool = True) -> Dict[str, Any]:
+        fabric: bool = True, xgmi_kernel: bool = False) -> Dict[str, Any]:
     """The cycle; returns the summary (never raises for a failed test: failures are in the result)."""
     from ..ops import diag
     from .agent import Agent
@@ -69,7 +69,8 @@ def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: 
     out["verdict"] = rep.get("state")
     if fabric and len(devices) >= 2:
         t1 = time.monotonic()
-        out["fabric"] = Agent._fabric_suite(list(devices), timeout_s)
+        extra = {"kernel": True} if xgmi_kernel else {}  # the kernel-driven xGMI passes and their attribution
+        out["fabric"] = Agent._fabric_suite(list(devices), timeout_s, **extra)
         out["fabric_wall_s"] = round(time.monotonic() - t1, 2)
     out["wall_s"] = round(time.monotonic() - t0, 2)
     return out
@@ -82,9 +83,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--timeout", type=float, default=150.0, help="per-device watchdog and RCCL deadline (s)")
     ap.add_argument("--parallel", type=int, default=8)
     ap.add_argument("--no-fabric", dest="fabric", action="store_false")
+    ap.add_argument("--xgmi-kernel", dest="xgmi_kernel", action="store_true",
+                    help="also load the xGMI links from a kernel and attribute slow copies to link or copy engine")
     args = ap.parse_args(argv)
     devices = [int(x) for x in args.devices.split(",") if x.strip()]
-    res = run(devices, args.level, args.timeout, args.parallel, args.fabric)
+    res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel)
     print(json.dumps(res, separators=(",", ":"), default=str), flush=True)
     return 0
 

@@ -9,6 +9,7 @@ artefact               source                                              toolc
 ``libmi355x_probe.so`` ``csrc/probe/probe.cpp`` (C ABI over libamd_smi)     g++ + /opt/rocm/lib/libamd_smi
 ``mi355x-probe``       ``csrc/probe/probe_main.cpp`` (standalone CLI)       g++ + libamd_smi
 ``libmi355x_diag.so``  ``csrc/diag/diag.hip`` (HIP kernels, gfx950 only)    hipcc --offload-arch=gfx950
+``libmi355x_xgmi.so``  ``csrc/xgmi/xgmi.hip`` (kernel-driven xGMI test)      hipcc --offload-arch=gfx950
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
@@ -72,6 +73,13 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "sources": [os.path.join(CSRC, "diag", "diag.hip")],
             "headers": [os.path.join(CSRC, "diag", "v4_plan.h"), os.path.join(CSRC, "diag", "valu_ref.h")],
             "out": os.path.join(OUT, "libmi355x_diag.so"),
+            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
+                    "-Wall", "-Wno-unused-result"],
+            "requires": hipcc,
+        },
+        "xgmi": {  # the diag target's line: plain HIP, no RCCL
+            "sources": [os.path.join(CSRC, "xgmi", "xgmi.hip")],
+            "out": os.path.join(OUT, "libmi355x_xgmi.so"),
             "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
                     "-Wall", "-Wno-unused-result"],
             "requires": hipcc,

@@ -990,7 +990,8 @@ def p2p_fan(src: int, dsts: List[int], mib: int = 256, iters: int = 5,
 
 
 def p2p_matrix(devices: Optional[list] = None, mib: int = 256, iters: int = 5,
-               timeout_s: Optional[float] = None, link: Optional[float] = None, fan: bool = True) -> Dict[str, Any]:
+               timeout_s: Optional[float] = None, link: Optional[float] = None, fan: bool = True,
+               kernel: bool = False) -> Dict[str, Any]:
     """Every ordered pair of ``devices`` (default: all): the node's xGMI fabric, link by link, then (``fan``) every
     source to all its peers at once.
 
@@ -1003,6 +1004,16 @@ def p2p_matrix(devices: Optional[list] = None, mib: int = 256, iters: int = 5,
     ``timeout_s`` bounds the whole matrix, both passes: each copy gets what is left of it, and the first that hangs
     ends the matrix (its devices are in an unknown state, with copies possibly still queued behind it), as does a
     deadline that passes between copies; both fail the test and name the pair or the source.
+
+    ``kernel``: after the copy passes, and inside the same deadline, the kernel-driven matrix
+    (``ops/xgmi.kernel_matrix``: the source's CUs store to and load from each peer, alone and all at once) runs and is
+    stored as ``out["kernel"]``.  Every copy-path problem about a pair's or a fan destination's rate then says whose it
+    is: ``link`` when the kernel's store rate of the same pair (alone for a pair problem, under the fan for a fan
+    problem) is slow too, else ``copy engine``, with both rates and the kernel median; a copy-path problem about bad
+    words likewise, by whether the kernel's stores arrived intact.  Kernel rows with bad words, a refused launch and
+    a hung launch fail the test; a kernel row that is merely slow while the copy path is fine is recorded in
+    ``kernel["slow"]`` only (no kernel rate has been measured on a hive: ``xgmi.KERNEL_MIN_GBPS``).  Off (the default):
+    no call into that library, no new key, every string as before.
     """
     devs = list(range(device_count())) if devices is None else list(devices)
     t0 = time.perf_counter()
@@ -1032,14 +1043,11 @@ def p2p_matrix(devices: Optional[list] = None, mib: int = 256, iters: int = 5,
     under = [p for p in pairs if p["gbps"] < floor and p not in slow]
     bad = [p for p in pairs if p["errors"]]
     nopeer = [p for p in pairs if not p["peer"]]
-    problems = (([stopped] if stopped else [])
-                + [f"{p['src']}->{p['dst']} {p['gbps']} GB/s" for p in slow]
-                + [f"{p['src']}->{p['dst']} {p['gbps']} GB/s under {floor:.0f} GB/s "
-                   f"({P2P_MIN_FRACTION_OF_LINK:.0%} of a {link:.0f} GB/s link)" for p in under]
-                + [f"{p['src']}->{p['dst']} {p['errors']} bad words" for p in bad]
-                + [f"{p['src']}->{p['dst']} no peer access" for p in nopeer])
     out: Dict[str, Any] = {"pairs": pairs, "median_gbps": median, "min_gbps": rates[0], "link_gbps": round(link, 1),
                            "floor_gbps": round(floor, 1)}
+    pair_stopped = stopped
+    fslow: List[Dict[str, Any]] = []
+    fbad: List[Dict[str, Any]] = []
     if fan and not stopped:
         fans: List[Dict[str, Any]] = []
         for a in devs:
@@ -1059,13 +1067,55 @@ def p2p_matrix(devices: Optional[list] = None, mib: int = 256, iters: int = 5,
         ffloor = P2P_FAN_MIN_FRACTION_OF_LINK * link
         fslow = [t for t in dests if t["gbps"] < P2P_MIN_FRACTION_OF_MEDIAN * fmed or t["gbps"] < ffloor]
         fbad = [t for t in dests if t["errors"]]
-        if stopped:
-            problems.insert(0, stopped)
-        problems += ([f"fan {t['src']}->{t['dst']} {t['gbps']} GB/s with every link of {t['src']} busy" for t in fslow]
-                     + [f"fan {t['src']}->{t['dst']} {t['errors']} bad words" for t in fbad])
         out["fan"] = {"sources": len(fans), "median_gbps": fmed, "min_gbps": frates[0],
                       "floor_gbps": round(ffloor, 1),
                       "total_gbps": {str(f["src"]): f["total_gbps"] for f in fans}, "to": dests}
+    fan_stopped = stopped if stopped != pair_stopped else ""
+    # the kernel-driven path (ops/xgmi.py), after the copy passes and inside the same deadline: its store rate of the
+    # same pair says whether a copy-path problem is the link's (slow for the CUs too) or the copy engine's
+    km: Optional[Dict[str, Any]] = None
+    if kernel and not stopped:
+        from . import xgmi
+        rest = left()
+        if rest is not None and rest <= 0:
+            stopped = f"deadline of {timeout_s:g} s passed before the kernel-driven passes"
+        else:
+            km = xgmi.kernel_matrix(devs, mib, iters, timeout_s=rest)
+            out["kernel"] = km
+            stopped = km.get("stopped", "")
+    kernel_stopped = stopped if stopped not in (pair_stopped, fan_stopped) else ""
+
+    def why(kind: str, p: Dict[str, Any], errors: bool = False) -> str:
+        """The attribution suffix of one copy-path problem, from the pair-alone or the fan row (``kind``) of its pair."""
+        if km is None:
+            return ""
+        rows = km["pairs"] if kind == "pair" else km["fan"]
+        row = next((r for r in rows if r["mode"] == "store" and (r["src"], r["dst"]) == (p["src"], p["dst"])), None)
+        if row is None:
+            return " (kernel stores not measured)"
+        if errors:
+            return (f" (link: kernel stores {row['errors']} bad words)" if row["errors"]
+                    else " (copy engine: kernel stores clean)")
+        link_too = any(s["kind"] == kind and s["mode"] == "store" and (s["src"], s["dst"]) == (p["src"], p["dst"])
+                       for s in km["slow"])
+        return (f" ({'link' if link_too else 'copy engine'}: kernel stores {row['gbps']} GB/s, "
+                f"median {km['median_gbps'][kind + '_store']})")
+    problems = (([pair_stopped] if pair_stopped else [])
+                + [f"{p['src']}->{p['dst']} {p['gbps']} GB/s{why('pair', p)}" for p in slow]
+                + [f"{p['src']}->{p['dst']} {p['gbps']} GB/s under {floor:.0f} GB/s "
+                   f"({P2P_MIN_FRACTION_OF_LINK:.0%} of a {link:.0f} GB/s link){why('pair', p)}" for p in under]
+                + [f"{p['src']}->{p['dst']} {p['errors']} bad words{why('pair', p, True)}" for p in bad]
+                + [f"{p['src']}->{p['dst']} no peer access" for p in nopeer])
+    if fan_stopped:
+        problems.insert(0, fan_stopped)
+    problems += ([f"fan {t['src']}->{t['dst']} {t['gbps']} GB/s with every link of {t['src']} busy{why('fan', t)}"
+                  for t in fslow]
+                 + [f"fan {t['src']}->{t['dst']} {t['errors']} bad words{why('fan', t, True)}" for t in fbad])
+    if kernel_stopped:
+        problems.insert(0, kernel_stopped)
+    if km is not None:  # what the kernel path itself fails a node for: wrong bytes, a refused or errored launch
+        problems += [f"kernel {r['mode']} {'fan ' if r['kind'] == 'fan' else ''}{r['src']}->{r['dst']} "
+                     f"{r['errors']} bad words" for r in km["bad"]] + list(km.get("failed", []))
     out.update({"pass": not problems, "wall_s": round(time.perf_counter() - t0, 3), "detail": "; ".join(problems[:8])})
     if stopped:
         out["stopped"] = stopped
@@ -1325,8 +1375,10 @@ P2P_SHARE = 0.45
 
 
 def fabric_tests(devices: List[int], p2p: bool = True, rccl: bool = True,
-                 timeout_s: Optional[float] = None, link: Optional[float] = None) -> Dict[str, Any]:
-    """The node-level tests of level 2: the xGMI pair matrix (within ``P2P_SHARE`` of ``timeout_s``) and the RCCL
+                 timeout_s: Optional[float] = None, link: Optional[float] = None,
+                 kernel: bool = False) -> Dict[str, Any]:
+    """The node-level tests of level 2: the xGMI pair matrix (within ``P2P_SHARE`` of ``timeout_s``; ``kernel``: with
+    the kernel-driven passes and their attribution, :func:`p2p_matrix`) and the RCCL
     collectives (within what is left up to 90 %, aborted at that deadline); without a timeout both wait as long
     as they take.  A test that raises is reported as failed; only a missing diag library propagates."""
     import time as _time
@@ -1334,7 +1386,9 @@ def fabric_tests(devices: List[int], p2p: bool = True, rccl: bool = True,
     t0 = _time.monotonic()
     if p2p:
         try:
-            out["p2p"] = p2p_matrix(devices, timeout_s=P2P_SHARE * timeout_s if timeout_s else None, link=link)
+            extra = {"kernel": True} if kernel else {}  # off: the call p2p_matrix has always got
+            out["p2p"] = p2p_matrix(devices, timeout_s=P2P_SHARE * timeout_s if timeout_s else None, link=link,
+                                    **extra)
         except NativeUnavailable:
             raise
         except Exception as e:  # a pair that errors out is a failed fabric, not a lost report
@@ -1406,7 +1460,8 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 
 def main(argv=None) -> int:
-    """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--format json|text]``:
+    """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
+    [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1419,6 +1474,9 @@ def main(argv=None) -> int:
     ap.add_argument("--no-p2p", dest="p2p", action="store_false", help="skip the level-2 xGMI pair matrix")
     ap.add_argument("--no-rccl", dest="rccl", action="store_false",
                     help="skip the level-2 RCCL collectives (ops/fabric.py)")
+    ap.add_argument("--xgmi-kernel", dest="xgmi_kernel", action="store_true",
+                    help="level 2: also load the xGMI links from a kernel (CU stores and loads) and say of every slow "
+                         "copy whether the link or the copy engine was slow")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1431,12 +1489,13 @@ def main(argv=None) -> int:
         print(f"result: FAIL ({msg})" if args.format == "text" else json.dumps({"devices": {}, "pass": False,
                                                                                 "error": msg}, indent=1))
         return 1
+    xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
     if args.duration > 0:
         import sys as _sys
         b = burn_in(args.level, devices, args.duration, max(1, args.parallel),
                     progress=lambda line: print(line, file=_sys.stderr, flush=True))
         if args.level >= 2 and (args.p2p or args.rccl):  # the node-level tests once, after the rounds
-            b["fabric"] = fabric_tests(devices, args.p2p, args.rccl, args.timeout or None)
+            b["fabric"] = fabric_tests(devices, args.p2p, args.rccl, args.timeout or None, **xk)
             b["pass"] = b["pass"] and all(r.get("pass") for r in b["fabric"].values())
         if args.format == "text":
             lines = [f"burn-in: {b['rounds']} rounds in {b['wall_s']} s on {len(devices)} GPU(s)"]
@@ -1466,7 +1525,7 @@ def main(argv=None) -> int:
         out["node"] = {"findings": findings, "warnings": [finding_text(f) for f in findings]}
     ok = all(t.get("pass") for d in out["devices"].values() for t in d["tests"].values())
     if args.level >= 2 and (args.p2p or args.rccl):
-        out["fabric"] = fabric_tests(devices, args.p2p, args.rccl, args.timeout or None)
+        out["fabric"] = fabric_tests(devices, args.p2p, args.rccl, args.timeout or None, **xk)
         ok = ok and all(r.get("pass") for r in out["fabric"].values())
     out["pass"] = ok
     print(render_text(out) if args.format == "text" else json.dumps(out, indent=1), end="" if args.format == "text" else "\n")

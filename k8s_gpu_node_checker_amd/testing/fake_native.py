@@ -1,7 +1,7 @@
-"""CPU stand-ins for the C ABIs of ``libmi355x_diag.so`` and ``libmi355x_fabric.so``.
+"""CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
-pointers), so ``ops/diag.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
+pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
 N healthy MI355X by default, with per-GPU rate factors, wrong-result counts, slow or peer-less GPU pairs
 and RCCL failures injectable.  Used by the CPU tests of the verdict logic and of whole 8-GPU agent
 cycles; the real libraries run under ``tests/test_gpu.py`` on an MI355X.
@@ -439,6 +439,78 @@ class FakeDiagLib:
         return 0
 
 
+def xgmi_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeXgmiLib` stands in for, read from csrc/xgmi/xgmi.hip the way
+    :func:`diag_c_exports` reads diag.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "xgmi", "xgmi.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(xgmi_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeXgmiLib:
+    """``libmi355x_xgmi.so`` for a node of ``n`` GPUs.
+
+    kernel_gbps:   rate of every destination, alone or under the fan, in both modes
+    kernel_slow:   ``{(src, dst, mode): rate}`` overrides it (``mode``: "store" | "load" for the pair-alone launch,
+                   "fan_store" | "fan_load" for that destination under the fan)
+    kernel_errors: ``{(src, dst, mode): bad elements}``, keyed the same way
+    hung:          ``(src, dst)`` pairs whose launch never completes: -4 at the deadline (it is waited out)
+    Calls are logged as ``xk{mode}{src}->{dsts}``."""
+
+    def __init__(self, n: int = 8, kernel_gbps: float = 55.0,
+                 kernel_slow: Optional[Dict[Tuple[int, int, str], float]] = None,
+                 kernel_errors: Optional[Dict[Tuple[int, int, str], int]] = None,
+                 hung: Tuple[Tuple[int, int], ...] = ()):
+        self.n, self.kernel_gbps = n, kernel_gbps
+        self.kernel_slow = dict(kernel_slow or {})
+        self.kernel_errors = dict(kernel_errors or {})
+        self.hung = set(hung)
+        self.release = threading.Event()
+        self.calls: List[str] = []
+        self.timeouts_ms: List[float] = []
+        self.err = b"boom"
+
+    def xgmi_last_error(self) -> bytes:
+        return self.err
+
+    def xgmi_device_count(self) -> int:
+        return self.n
+
+    def xgmi_kernel_fan(self, src, dsts, ndst, nbytes, iters, mode, timeout_ms, inject_dst, inject_word, gbps, errors,
+                        first_bad, peer, total):
+        name = ("store", "load")[mode]
+        peers = [dsts[i] for i in range(ndst)]
+        self.calls.append(f"xk{name}{src}->{','.join(map(str, peers))}")
+        self.timeouts_ms.append(float(timeout_ms))
+        if not 0 <= src < self.n or not 1 <= ndst <= 64 or any(not 0 <= d < self.n for d in peers) or nbytes < 16:
+            self.err = b"xgmi kernel fan: need a valid source, 1..64 destinations, iters >= 1, bytes >= 16"
+            return -2
+        for d in peers:
+            if (src, d) in self.hung:
+                if timeout_ms > 0:
+                    self.release.wait(timeout_ms / 1000.0)
+                else:
+                    self.release.wait()
+                if not self.release.is_set():
+                    self.err = b"xgmi kernel %s %d->%d: the launches did not complete within %d ms (xGMI link hung)" % (
+                        name.encode(), src, d, int(timeout_ms))
+                    return -4
+        key = name if ndst == 1 else "fan_" + name
+        for i, d in enumerate(peers):
+            gbps[i] = self.kernel_slow.get((src, d, key), self.kernel_gbps)
+            errors[i] = self.kernel_errors.get((src, d, key), 0)
+            first_bad[i] = 0 if errors[i] else (1 << 64) - 1
+            peer[i] = 1
+        _put(total, ctypes.c_double, float(sum(gbps[i] for i in range(ndst))))
+        return 0
+
+
 class FakeFabricLib:
     """``libmi355x_fabric.so`` (in-process RCCL communicator over the node's GPUs)."""
 
@@ -522,9 +594,9 @@ class NarrowedDiagLib:
         return on_physical
 
 
-def install(n: int = 1, fabric: Optional[Dict] = None, **diag_kw) -> None:
-    """Make this process's ``ops.diag`` and ``ops.fabric`` use the fakes: ``FakeDiagLib(n, **diag_kw)`` and
-    ``FakeFabricLib(**fabric)``.  The node agent's diagnostic children run it first when the agent is given
+def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, **diag_kw) -> None:
+    """Make this process's ``ops.diag``, ``ops.fabric`` and ``ops.xgmi`` use the fakes: ``FakeDiagLib(n, **diag_kw)``,
+    ``FakeFabricLib(**fabric)`` and ``FakeXgmiLib(n, **xgmi)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
     child code path runs unchanged on CPU with scripted GPUs; a child narrowed to one GPU (``HIP_VISIBLE_DEVICES``)
     sees only that one, as under HIP."""
@@ -537,3 +609,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, **diag_kw) -> None:
         lib = NarrowedDiagLib(lib, int(vis))  # type: ignore[arg-type]
     diag.lib = lambda: lib
     fabric_mod._lib = FakeFabricLib(**(fabric or {}))
+    from ..ops import xgmi as xgmi_mod
+    xlib = FakeXgmiLib(n=n, **(xgmi or {}))
+    xgmi_mod.lib = lambda: xlib
