@@ -443,8 +443,10 @@ class Agent:
                  pod_resources_socket: Optional[str] = None, gpu_resources: Sequence[str] = (PRIMARY_GPU_KEY,),
                  label_node: bool = False, annotation_encoding: str = "json", diag_parallel: int = DIAG_PARALLEL,
                  diag_baseline: bool = True, baseline_file: Optional[str] = None, isolation: str = "thread",
-                 diag_setup: Optional[tuple] = None, diag_xgmi_kernel: bool = False):
+                 diag_setup: Optional[tuple] = None, diag_xgmi_kernel: bool = False,
+                 diag_atomics: bool = False):
         self.node = node
+        self.diag_atomics = diag_atomics  # every device's suite also runs the atomics diagnostic (ops/atomics.py)
         self.diag_xgmi_kernel = diag_xgmi_kernel  # the node-level suite also runs the kernel-driven xGMI passes
         if isolation not in ISOLATION:
             raise ValueError(f"isolation must be one of {ISOLATION}")
@@ -890,6 +892,8 @@ class Agent:
         # the host-link turn is waited for only within this device's watchdog (a GPU stuck in its turn is that
         # GPU's hang, not every GPU's); CLOCK_MONOTONIC is one clock for the agent and its children
         kw["deadline"] = time.monotonic() + 0.9 * self.diag_timeout
+        if self.diag_atomics:
+            kw["extra"] = ("atomics",)
         job = self.workers.device(self.diag_level, d, kw, self._diag_done, host)
         self._diag_threads[d] = _DiagRun(job, time.time(), time.monotonic())
 
@@ -1166,6 +1170,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--diag-xgmi-kernel", action="store_true",
                     help="level 2: after the xGMI copy passes, load the links from a kernel too (CU stores and loads), "
                          "and say of every slow copy whether the link or the copy engine was slow")
+    ap.add_argument("--diag-atomics", action="store_true",
+                    help="every GPU's diagnostics also run the atomics test: atomic adds, max, xor and returning adds "
+                         "from every XCD onto one array, every element checked")
     ap.add_argument("--diag-isolation", choices=ISOLATION, default="process",
                     help="process (default): each cycle's HIP diagnostics run in disposable child processes, so the "
                          "agent never initialises HIP, a hung one is SIGKILLed at --diag-timeout and a GPU fault "
@@ -1232,7 +1239,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                   gpu_resources=tuple(args.gpu_resource or (PRIMARY_GPU_KEY,)), label_node=args.label_node,
                   annotation_encoding=args.annotation_encoding, diag_parallel=args.diag_parallel,
                   diag_baseline=args.diag_baseline, baseline_file=args.diag_baseline_file,
-                  isolation=args.diag_isolation, diag_xgmi_kernel=args.diag_xgmi_kernel)
+                  isolation=args.diag_isolation, diag_xgmi_kernel=args.diag_xgmi_kernel,
+                  diag_atomics=args.diag_atomics)
     if args.diag_baseline_reset and agent.baselines is not None:
         spec = args.diag_baseline_reset.strip()
         gone = agent.baselines.drop(None if spec.lower() == "all" else spec.split(","))

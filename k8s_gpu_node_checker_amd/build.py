@@ -1,6 +1,6 @@
 """Build every native component in-tree (``k8s_gpu_node_checker_amd/_native/``).
 
-``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag] [--force]``
+``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics] [--force]``
 
 =====================  ==================================================  ==========================
 artefact               source                                              toolchain
@@ -10,6 +10,7 @@ artefact               source                                              toolc
 ``mi355x-probe``       ``csrc/probe/probe_main.cpp`` (standalone CLI)       g++ + libamd_smi
 ``libmi355x_diag.so``  ``csrc/diag/diag.hip`` (HIP kernels, gfx950 only)    hipcc --offload-arch=gfx950
 ``libmi355x_xgmi.so``  ``csrc/xgmi/xgmi.hip`` (kernel-driven xGMI test)      hipcc --offload-arch=gfx950
+``libmi355x_atomics.so`` ``csrc/atomics/atomics.hip`` (atomics diagnostic)      hipcc --offload-arch=gfx950
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
@@ -84,6 +85,14 @@ def _targets() -> Dict[str, Dict[str, object]]:
                     "-Wall", "-Wno-unused-result"],
             "requires": hipcc,
         },
+        "atomics": {  # the xgmi target's line
+            "sources": [os.path.join(CSRC, "atomics", "atomics.hip")],
+            "headers": [os.path.join(CSRC, "atomics", "atomics_ref.h")],
+            "out": os.path.join(OUT, "libmi355x_atomics.so"),
+            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
+                    "-Wall", "-Wno-unused-result"],
+            "requires": hipcc,
+        },
         "fabric": {
             "sources": [os.path.join(CSRC, "fabric", "fabric.hip")],
             "out": os.path.join(OUT, "libmi355x_fabric.so"),
@@ -154,7 +163,7 @@ def build(only: Optional[Sequence[str]] = None, force: bool = False, verbose: bo
 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--only", help="comma list of fastpath,probe,diag")
+    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,fabric")
     ap.add_argument("--force", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)

@@ -1,0 +1,436 @@
+// libmi355x_atomics.so: the atomics diagnostic (HIP, gfx950).
+//
+// On gfx950 a global atomic executes at the memory side, not in the CU and not in the L2: each wave-instruction
+// leaves the L2 as uncached 64-byte atomic requests.  No ALU, LDS, L2-read or HBM-stream test therefore shows a
+// broken atomic adder, an add lost when several XCDs hit one address, or a wrong returned value; this library does.
+// ops/atomics.py is its Python side; ops/diag.run(extra=("atomics",)) runs it next to a level's own tests.
+//
+// A target array of `words` elements in ordinary hipMalloc memory; every element receives `adders` atomic
+// operations.  A kind is three launches per iteration, and visibility between them comes from the kernel boundary
+// alone (no spin loop, no flag, no wait between workgroups: every launch ends by itself):
+//   fill     plain stores of each element's hash-derived initial value
+//   atomics  workgroup g carries adder a = g % adders for slice g / adders of the words, so with the round-robin
+//            deal of workgroups over the XCDs the adders of one address come from different XCDs; every wave reads
+//            XCC_ID and counts itself, so the placement is reported, not assumed.  One element per lane: a
+//            wave-instruction covers 64 consecutive elements (256 contiguous bytes, 512 for the 64-bit kinds)
+//   verify   plain loads; each element is held against atomics_expected() (atomics_ref.h), bit for bit: wrong
+//            elements are counted and the lowest wrong index kept
+// It carries its own copies of the few host helpers it shares with diag.hip and xgmi.hip (DevBuf, Timer): their C
+// ABIs are pinned by the tests and stay untouched.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+#include "atomics_ref.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+#define ATOMICS_CHECK(expr)                                                               \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) {                                                               \
+      (void)hipGetLastError(); /* a failed allocation must not fail the next call's check */ \
+      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
+      return -1;                                                                          \
+    }                                                                                     \
+  } while (0)
+
+constexpr unsigned THREADS = 256;
+constexpr int XCDS = 8;
+constexpr size_t MAX_WORDS = 1ULL << 31;  // 16 GiB of 64-bit elements
+
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// what one launch reports (device memory, zeroed by the host before the launch that fills it)
+struct Stats {
+  unsigned long long errors;     // verify: wrong elements (ticket: plus tickets returned out of range)
+  unsigned long long first_bad;  // verify: the lowest wrong element (~0: none)
+  unsigned long long ops;        // atomics: atomic operations issued
+  unsigned long long waves[XCDS];  // atomics: waves that ran on each XCD
+};
+
+__device__ __forceinline__ void count_wave(Stats* st) {
+  if ((threadIdx.x & 63u) == 0) {
+    const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID[3:0]
+    atomicAdd(&st->waves[xcc & 7u], 1ULL);
+  }
+}
+
+template <int KIND>
+__device__ __forceinline__ void store_bits(void* buf, size_t i, uint64_t bits) {
+  if constexpr (KIND == ATOMICS_ADD_U64 || KIND == ATOMICS_ADD_F64)
+    static_cast<unsigned long long*>(buf)[i] = bits;
+  else
+    static_cast<unsigned int*>(buf)[i] = static_cast<unsigned int>(bits);
+}
+
+template <int KIND>
+__device__ __forceinline__ uint64_t load_bits(const void* buf, size_t i) {
+  if constexpr (KIND == ATOMICS_ADD_U64 || KIND == ATOMICS_ADD_F64)
+    return static_cast<const unsigned long long*>(buf)[i];
+  else
+    return static_cast<const unsigned int*>(buf)[i];
+}
+
+// one no-return atomic of the kind's own instruction on element i
+template <int KIND>
+__device__ __forceinline__ void apply(void* buf, size_t i, uint64_t bits) {
+  if constexpr (KIND == ATOMICS_ADD_U32) {
+    atomicAdd(static_cast<unsigned int*>(buf) + i, static_cast<unsigned int>(bits));
+  } else if constexpr (KIND == ATOMICS_ADD_U64) {
+    atomicAdd(static_cast<unsigned long long*>(buf) + i, static_cast<unsigned long long>(bits));
+  } else if constexpr (KIND == ATOMICS_ADD_F32) {
+    atomicAdd(static_cast<float*>(buf) + i, __uint_as_float(static_cast<unsigned int>(bits)));
+  } else if constexpr (KIND == ATOMICS_ADD_F64) {
+    atomicAdd(static_cast<double*>(buf) + i, __longlong_as_double(static_cast<long long>(bits)));
+  } else if constexpr (KIND == ATOMICS_PK_BF16) {
+    const unsigned int u = static_cast<unsigned int>(bits);
+    bf16x2 v;
+    __builtin_memcpy(&v, &u, sizeof v);
+    typedef __attribute__((address_space(1))) bf16x2* global_bf16x2_ptr;  // the builtin takes a global pointer
+    __builtin_amdgcn_global_atomic_fadd_v2bf16((global_bf16x2_ptr)(static_cast<unsigned int*>(buf) + i), v);
+  } else if constexpr (KIND == ATOMICS_MAX_U32) {
+    atomicMax(static_cast<unsigned int*>(buf) + i, static_cast<unsigned int>(bits));
+  } else {
+    atomicXor(static_cast<unsigned int*>(buf) + i, static_cast<unsigned int>(bits));
+  }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(THREADS) fill_kernel(void* buf, size_t words, uint64_t seed) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * THREADS;
+  for (size_t i = blockIdx.x * static_cast<size_t>(THREADS) + threadIdx.x; i < words; i += stride)
+    store_bits<KIND>(buf, i, atomics_init(KIND, i, seed));
+}
+
+// Workgroup g: adder g % adders, slice g / adders of `slices`; a slice is the chunks of THREADS consecutive
+// elements s, s + slices, ...  (drop_word, drop_adder): the self-check's one lost operation (-1: none).
+template <int KIND>
+__global__ void __launch_bounds__(THREADS) atomics_kernel(void* buf, size_t words, unsigned adders, unsigned slices,
+                                                          uint64_t seed, long long drop_word, int drop_adder,
+                                                          Stats* st) {
+  count_wave(st);
+  const int a = static_cast<int>(blockIdx.x % adders);
+  const size_t stride = static_cast<size_t>(slices) * THREADS;
+  unsigned long long issued = 0;
+  for (size_t i = (blockIdx.x / adders) * static_cast<size_t>(THREADS) + threadIdx.x; i < words; i += stride) {
+    if (a == drop_adder && static_cast<long long>(i) == drop_word) continue;
+    apply<KIND>(buf, i, atomics_operand(KIND, i, a, seed));
+    ++issued;
+  }
+  if (issued) atomicAdd(&st->ops, issued);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(THREADS) verify_kernel(const void* buf, size_t words, int adders, uint64_t seed,
+                                                         Stats* st) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * THREADS;
+  for (size_t i = blockIdx.x * static_cast<size_t>(THREADS) + threadIdx.x; i < words; i += stride) {
+    if (load_bits<KIND>(buf, i) != atomics_expected(KIND, i, adders, seed)) {
+      atomicAdd(&st->errors, 1ULL);
+      atomicMin(&st->first_bad, static_cast<unsigned long long>(i));
+    }
+  }
+}
+
+// The ticket kind: hits[0 .. plan.hits()) then the counters, one allocation, zero-filled by fill_kernel's twin.
+__global__ void __launch_bounds__(THREADS) ticket_fill_kernel(unsigned int* p, size_t n) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * THREADS;
+  for (size_t i = blockIdx.x * static_cast<size_t>(THREADS) + threadIdx.x; i < n; i += stride) p[i] = 0u;
+}
+
+__global__ void __launch_bounds__(THREADS) ticket_kernel(unsigned int* hits, AtomicsTicketPlan plan, unsigned adders,
+                                                         unsigned slices, long long drop_word, int drop_adder,
+                                                         Stats* st) {
+  count_wave(st);
+  unsigned int* ctr = hits + plan.hits();
+  const int a = static_cast<int>(blockIdx.x % adders);
+  const size_t stride = static_cast<size_t>(slices) * THREADS;
+  unsigned long long issued = 0, beyond = 0;
+  for (size_t i = (blockIdx.x / adders) * static_cast<size_t>(THREADS) + threadIdx.x; i < plan.words; i += stride) {
+    if (a == drop_adder && static_cast<long long>(i) == drop_word) continue;
+    const size_t c = i % plan.counters;            // 64 consecutive lanes: 64 different counters
+    const unsigned int t = atomicAdd(ctr + c, 1u);  // the returning form: its value is used
+    ++issued;
+    if (t < plan.tickets) {  // a wrong return is counted, never followed out of the array
+      atomicAdd(hits + c * plan.tickets + t, 1u);
+      ++issued;
+    } else {
+      ++beyond;
+    }
+  }
+  if (issued) atomicAdd(&st->ops, issued);
+  if (beyond) atomicAdd(&st->errors, beyond);
+}
+
+__global__ void __launch_bounds__(THREADS) ticket_verify_kernel(const unsigned int* hits, AtomicsTicketPlan plan,
+                                                                int adders, Stats* st) {
+  const size_t n = plan.elements();
+  const size_t stride = static_cast<size_t>(gridDim.x) * THREADS;
+  for (size_t e = blockIdx.x * static_cast<size_t>(THREADS) + threadIdx.x; e < n; e += stride) {
+    if (hits[e] != atomics_ticket_expected(plan, e, adders)) {
+      atomicAdd(&st->errors, 1ULL);
+      atomicMin(&st->first_bad, static_cast<unsigned long long>(e));
+    }
+  }
+}
+
+int cu_count(int device) {
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    cus = 256;  // the MI355X's CU count (a grid size only: any value is correct, this one fills the chip)
+  }
+  return cus;
+}
+
+// grid of the grid-stride fill / verify kernels: 8 workgroups per CU, never more than one thread per element
+unsigned flat_grid(int cus, size_t n) {
+  return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((n + THREADS - 1) / THREADS, static_cast<size_t>(cus) * 8)));
+}
+
+// slices of the atomics launch: about 8 workgroups per CU in all (slices * adders), never more than one per chunk
+unsigned slice_count(int cus, size_t n, int adders) {
+  const size_t want = std::max<size_t>(1, static_cast<size_t>(cus) * 8 / static_cast<size_t>(adders));
+  return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((n + THREADS - 1) / THREADS, want)));
+}
+
+// Device allocation, freed on every return path.
+struct DevBuf {
+  void* ptr = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes); }
+  ~DevBuf() {
+    if (ptr) (void)hipFree(ptr);
+  }
+};
+
+// A pair of events, released on every return path.
+struct Timer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Timer() = default;
+  Timer(const Timer&) = delete;
+  Timer& operator=(const Timer&) = delete;
+  hipError_t create() {
+    hipError_t e = hipEventCreate(&e0);
+    return e == hipSuccess ? hipEventCreate(&e1) : e;
+  }
+  ~Timer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+// Self-check hook (as xgmi.hip's flip_word): bit 4 of the element's low 32-bit word is flipped from the host.
+int flip_element(void* buf, size_t elem, int elem_bytes) {
+  uint32_t* w = reinterpret_cast<uint32_t*>(static_cast<char*>(buf) + elem * static_cast<size_t>(elem_bytes));
+  uint32_t v = 0;
+  ATOMICS_CHECK(hipMemcpy(&v, w, sizeof v, hipMemcpyDeviceToHost));
+  v ^= 0x10u;
+  ATOMICS_CHECK(hipMemcpy(w, &v, sizeof v, hipMemcpyHostToDevice));
+  return 0;
+}
+
+struct Launch {
+  void* buf;
+  size_t words;
+  int adders;
+  uint64_t seed;
+  int cus;
+  Stats* st;
+};
+
+template <int KIND>
+void launch_fill(const Launch& l) {
+  hipLaunchKernelGGL(fill_kernel<KIND>, dim3(flat_grid(l.cus, l.words)), dim3(THREADS), 0, nullptr, l.buf, l.words, l.seed);
+}
+template <int KIND>
+void launch_atomics(const Launch& l, long long drop_word, int drop_adder) {
+  const unsigned slices = slice_count(l.cus, l.words, l.adders);
+  hipLaunchKernelGGL(atomics_kernel<KIND>, dim3(slices * static_cast<unsigned>(l.adders)), dim3(THREADS), 0, nullptr, l.buf,
+                     l.words, static_cast<unsigned>(l.adders), slices, l.seed, drop_word, drop_adder, l.st);
+}
+template <int KIND>
+void launch_verify(const Launch& l) {
+  hipLaunchKernelGGL(verify_kernel<KIND>, dim3(flat_grid(l.cus, l.words)), dim3(THREADS), 0, nullptr,
+                     static_cast<const void*>(l.buf), l.words, l.adders, l.seed, l.st);
+}
+
+// phase 0 fill, 1 atomics, 2 verify, of kind `kind`
+void launch(int kind, int phase, const Launch& l, long long drop_word, int drop_adder) {
+  if (kind == ATOMICS_TICKET) {
+    const AtomicsTicketPlan plan = atomics_ticket_plan(l.words, l.adders);
+    unsigned int* hits = static_cast<unsigned int*>(l.buf);
+    if (phase == 0) {
+      hipLaunchKernelGGL(ticket_fill_kernel, dim3(flat_grid(l.cus, plan.elements())), dim3(THREADS), 0, nullptr, hits,
+                         static_cast<size_t>(plan.elements()));
+    } else if (phase == 1) {
+      const unsigned slices = slice_count(l.cus, plan.words, l.adders);
+      hipLaunchKernelGGL(ticket_kernel, dim3(slices * static_cast<unsigned>(l.adders)), dim3(THREADS), 0, nullptr, hits, plan,
+                         static_cast<unsigned>(l.adders), slices, drop_word, drop_adder, l.st);
+    } else {
+      hipLaunchKernelGGL(ticket_verify_kernel, dim3(flat_grid(l.cus, plan.elements())), dim3(THREADS), 0, nullptr,
+                         static_cast<const unsigned int*>(hits), plan, l.adders, l.st);
+    }
+    return;
+  }
+#define ATOMICS_PHASES(K)                        \
+  case K:                                        \
+    if (phase == 0)                              \
+      launch_fill<K>(l);                         \
+    else if (phase == 1)                         \
+      launch_atomics<K>(l, drop_word, drop_adder); \
+    else                                         \
+      launch_verify<K>(l);                       \
+    break;
+  switch (kind) {
+    ATOMICS_PHASES(ATOMICS_ADD_U32)
+    ATOMICS_PHASES(ATOMICS_ADD_U64)
+    ATOMICS_PHASES(ATOMICS_ADD_F32)
+    ATOMICS_PHASES(ATOMICS_ADD_F64)
+    ATOMICS_PHASES(ATOMICS_PK_BF16)
+    ATOMICS_PHASES(ATOMICS_MAX_U32)
+    ATOMICS_PHASES(ATOMICS_XOR_U32)
+  }
+#undef ATOMICS_PHASES
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* atomics_last_error(void) { return g_err.c_str(); }
+
+int atomics_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return n;
+}
+
+// Every kind whose bit is set in `kind_mask` (bit k: AtomicsKind k of atomics_ref.h), one after the other, on
+// `words` elements with `adders` operations each.  Per kind: `iters` iterations of fill, atomics, verify; only the
+// atomics launch is timed (HIP events), ms[k] is the mean of the iterations.  Every iteration is verified, so
+// errors[k] adds up over them; first_bad[k] is the lowest wrong element of the first iteration that had one (~0:
+// none), got[k] its 64 bits as read back by the host after that verification, want[k] atomics_expected() of it.
+// ops[k] and xcd_waves[8 * k + x] (waves that ran on XCD x) are the last iteration's atomics launch alone.
+// The ticket kind runs on at most 2^20 elements (atomics_ticket_plan); its elements, for first_bad and inject_word,
+// are its hit words followed by its counters, 4 bytes each.
+//
+// Refused with -2 and a message: adders outside 1..32 (beyond it the float kinds' sums are no longer exact), words
+// outside 1..2^31, iters < 1, an unknown kind, a hook outside the array.
+//
+// Self-check hooks, both off by default (inject_kind -1, inject_drop_adder -1), both acting on the last iteration of
+// kind `inject_kind` only, both on element `inject_word`:
+//   flip  (inject_drop_adder < 0): the host flips one bit of the element between the atomics launch and the verify
+//         launch: 1 wrong element, got = want ^ 0x10
+//   drop  (inject_drop_adder >= 0): the one lane that would apply that adder's operation to the element skips it:
+//         1 wrong element, got = want_without[k] = atomics_expected() without that operand -- a lost add, told from a
+//         flipped bit.  For the ticket kind inject_word is the drawing element (below the words that take part), and
+//         the wrong elements are its counter and that counter's last hit word.
+// want_without[k] is 0 unless the drop hook is on for kind k (and is not defined for the ticket kind).
+int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, uint64_t seed, int iters, int inject_kind,
+                 long long inject_word, int inject_drop_adder, unsigned long long* errors,
+                 unsigned long long* first_bad, unsigned long long* got, unsigned long long* want,
+                 unsigned long long* want_without, unsigned long long* ops, unsigned long long* xcd_waves, double* ms) {
+  int n = 0;
+  ATOMICS_CHECK(hipGetDeviceCount(&n));
+  if (device < 0 || device >= n || words < 1 || words > MAX_WORDS || adders < 1 || adders > ATOMICS_MAX_ADDERS ||
+      iters < 1 || !kind_mask || (kind_mask >> ATOMICS_KINDS)) {
+    g_err = "atomics test: need a valid device, words 1..2^31, adders 1..32 (the float kinds' sums are exact up to "
+            "there), iters >= 1 and a mask of known kinds";
+    return -2;
+  }
+  const AtomicsTicketPlan plan = atomics_ticket_plan(words, adders);
+  if (inject_kind >= ATOMICS_KINDS || inject_drop_adder >= adders) {
+    g_err = "atomics test: inject_kind must be a kind and inject_drop_adder below adders";
+    return -2;
+  }
+  if (inject_kind >= 0) {
+    const bool drop = inject_drop_adder >= 0;
+    const uint64_t limit = inject_kind != ATOMICS_TICKET ? words : (drop ? plan.words : plan.elements());
+    if (!((kind_mask >> inject_kind) & 1u) || inject_word < 0 || static_cast<uint64_t>(inject_word) >= limit) {
+      g_err = "atomics test: inject_kind must be in the mask and inject_word inside its array";
+      return -2;
+    }
+  }
+  for (int k = 0; k < ATOMICS_KINDS; ++k) {
+    errors[k] = got[k] = want[k] = want_without[k] = ops[k] = 0;
+    first_bad[k] = ~0ULL;
+    ms[k] = 0.0;
+    for (int x = 0; x < XCDS; ++x) xcd_waves[XCDS * k + x] = 0;
+  }
+  int cur = 0;
+  ATOMICS_CHECK(hipGetDevice(&cur));
+  ATOMICS_CHECK(hipSetDevice(device));
+  const int cus = cu_count(device);
+  DevBuf buf, stats;
+  const size_t array_bytes = (kind_mask & ~(1u << ATOMICS_TICKET)) ? words * 8 : 0;  // the widest kind's
+  const size_t ticket_bytes = ((kind_mask >> ATOMICS_TICKET) & 1u) ? plan.elements() * sizeof(unsigned int) : 0;
+  ATOMICS_CHECK(buf.alloc(std::max(array_bytes, ticket_bytes)));
+  ATOMICS_CHECK(stats.alloc(2 * sizeof(Stats)));  // [0] the atomics launch's, [1] the verify launch's
+  Stats* dst = static_cast<Stats*>(stats.ptr);
+  Timer tm;
+  ATOMICS_CHECK(tm.create());
+  Stats zero[2] = {};
+  zero[0].first_bad = zero[1].first_bad = ~0ULL;
+  for (int k = 0; k < ATOMICS_KINDS; ++k) {
+    if (!((kind_mask >> k) & 1u)) continue;
+    const int elem_bytes = atomics_elem_bytes(k);
+    const uint64_t kseed = seed + 0x632BE59BD9B4E019ULL * static_cast<uint64_t>(k + 1);
+    double total_ms = 0.0;
+    for (int it = 0; it < iters; ++it) {
+      const bool hooked = k == inject_kind && it == iters - 1;
+      const bool drop = hooked && inject_drop_adder >= 0;
+      Launch l = {buf.ptr, words, adders, kseed + static_cast<uint64_t>(it), cus, dst};
+      ATOMICS_CHECK(hipMemcpy(dst, zero, sizeof zero, hipMemcpyHostToDevice));
+      launch(k, 0, l, -1, -1);
+      ATOMICS_CHECK(hipGetLastError());
+      ATOMICS_CHECK(hipEventRecord(tm.e0, nullptr));
+      launch(k, 1, l, drop ? inject_word : -1, drop ? inject_drop_adder : -1);
+      ATOMICS_CHECK(hipGetLastError());
+      ATOMICS_CHECK(hipEventRecord(tm.e1, nullptr));
+      ATOMICS_CHECK(hipEventSynchronize(tm.e1));
+      if (hooked && !drop)
+        if (const int rc = flip_element(buf.ptr, static_cast<size_t>(inject_word), elem_bytes)) return rc;
+      l.st = dst + 1;
+      launch(k, 2, l, -1, -1);
+      ATOMICS_CHECK(hipGetLastError());
+      ATOMICS_CHECK(hipDeviceSynchronize());
+      float t = 0.f;
+      ATOMICS_CHECK(hipEventElapsedTime(&t, tm.e0, tm.e1));
+      total_ms += t;
+      Stats h[2];
+      ATOMICS_CHECK(hipMemcpy(h, dst, sizeof h, hipMemcpyDeviceToHost));
+      errors[k] += h[0].errors + h[1].errors;  // [0]: tickets returned out of range
+      ops[k] = h[0].ops;
+      for (int x = 0; x < XCDS; ++x) xcd_waves[XCDS * k + x] = h[0].waves[x];
+      if (h[1].first_bad != ~0ULL && first_bad[k] == ~0ULL) {
+        const uint64_t e = h[1].first_bad;
+        first_bad[k] = e;
+        unsigned long long g = 0;
+        ATOMICS_CHECK(hipMemcpy(&g, static_cast<char*>(buf.ptr) + e * static_cast<size_t>(elem_bytes),
+                                static_cast<size_t>(elem_bytes), hipMemcpyDeviceToHost));
+        got[k] = g;
+        want[k] = k == ATOMICS_TICKET ? atomics_ticket_expected(plan, e, adders) : atomics_expected(k, e, adders, l.seed);
+      }
+      if (drop && k != ATOMICS_TICKET)
+        want_without[k] = atomics_expected(k, static_cast<uint64_t>(inject_word), adders, l.seed, inject_drop_adder);
+    }
+    ms[k] = total_ms / iters;
+  }
+  ATOMICS_CHECK(hipSetDevice(cur));
+  return 0;
+}
+
+}  // extern "C"

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import threading
 import time
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .native import NativeUnavailable, load_cdll
 
@@ -154,6 +154,7 @@ KERNEL_REVISION: Dict[str, str] = {
     "host_link": "pinned-r1",
     "valu": "chains8x4-r1",      # 8 chains x 4 steps per iteration, 2 workgroups per CU
     "regfile": "v8-255+a0-255",  # no rate verdict: the stamp says which registers a clean result covered
+    "atomics": "8kinds-lane-per-element-r1",  # no rate verdict either (ops/atomics.py): which kinds a clean result covered
 }
 
 
@@ -847,6 +848,14 @@ def valu_burn(device: int = 0, kinds=VALU_KINDS, iters: int = 2000, reps: int = 
                  iters, reps, scale, inject_block)
 
 
+def atomics_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in atomics diagnostic (``ops/atomics.atomics_test``, its own library): every element of an array gets
+    atomic operations from workgroups on every XCD and is checked bit for bit.  No level runs it; ``run(extra=
+    ("atomics",))`` does."""
+    from . import atomics  # lazily: only who asks for the test needs libmi355x_atomics.so
+    return atomics.atomics_test(device, **kw)
+
+
 def _xcd_slices(fn: str, name: str, device: int, slice_bytes: int, passes: int, blocks_per_cu: int, seed: int,
                 inject_xcd: int, inject_word: int, *more: Any) -> Tuple[float, int, List[int], Dict[str, Any], str]:
     """What :func:`l2_bandwidth` and :func:`hbm_xcd` share: the call (``more`` = further out-parameters of ``fn``) and
@@ -1148,8 +1157,9 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "gemm": ("gemm", {}), "gemm_fp8": ("gemm_fp8", {}), "hbm": ("hbm", {}), "hbm_xcd": ("hbm_xcd", {}),
     "memtest": ("memtest", {}), "mfma": ("mfma_burn", {}), "lds": ("lds_test", {}), "l2": ("l2_bandwidth", {}),
     "valu": ("valu_burn", {}), "regfile": ("regfile_test", {}), "host_link": ("host_link", {}),
+    "atomics": ("atomics_test", {}),  # in no level: run(extra=("atomics",))
 }
-_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test"))  # error counts only: nothing to scale
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test"))  # error counts only: nothing to scale
 
 
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
@@ -1210,16 +1220,17 @@ def use_host_lock(lock: Any, cell: Any, label: Optional[int] = None) -> None:
 
 def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
-        deadline: Optional[float] = None) -> Dict[str, Dict[str, Any]]:
+        deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test).
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``),
+    each treated as the level's own are.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
     lands below the degraded line is measured once more and the better of the two is reported.  Tests of
     host resources (SHARED_TESTS) hold a process-wide lock, so concurrent per-GPU runs take turns there; a device
     that cannot get its turn before ``deadline`` (monotonic) reports that test ``skipped``, naming the holder."""
     out: Dict[str, Dict[str, Any]] = {}
-    tests = LEVELS.get(level, ())
+    tests = tuple(LEVELS.get(level, ())) + tuple(extra)
     if tests and scale is None:
         try:
             scale = device_scale(device, memory_partition, power_fraction)
@@ -1276,6 +1287,12 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         m = r.get("map") or {}
         kinds = " · ".join(f"{k} {v.get('gops', 0):.0f}" for k, v in (r.get("kinds") or {}).items())
         return f"{kinds} GOP/s; {m.get('cus', '?')} CUs, XCD spread {m.get('slowest_rel', 1.0):.3f}"
+    if test == "atomics":
+        kinds = r.get("kinds") or {}
+        xcds = sorted({v.get("xcds") for v in kinds.values()} - {None})
+        rates = " · ".join(f"{k} {v.get('gbs', 0):.0f}" for k, v in kinds.items())
+        return (f"{r.get('words', '?')} elements x {r.get('adders', '?')} adders from "
+                f"{'/'.join(map(str, xcds)) or '?'} XCDs, {r.get('errors', 0)} wrong; {rates} GB/s")
     if test == "regfile":
         return (f"{r.get('simds', '?')} SIMDs x {r.get('bytes_per_simd', 0) // 1024} KiB "
                 f"({r.get('regs_per_lane', '?')} registers), {r.get('errors', 0)} bad words")
@@ -1337,16 +1354,18 @@ def render_text(out: Dict[str, Any]) -> str:
     return "\n".join(lines) + "\n"
 
 
-def run_devices(level: int, devices: List[int], parallel: int = 8) -> Dict[int, Dict[str, Dict[str, Any]]]:
+def run_devices(level: int, devices: List[int], parallel: int = 8,
+                extra: Sequence[str] = ()) -> Dict[int, Dict[str, Dict[str, Any]]]:
     """:func:`run` on every device, at most ``parallel`` at once (one host thread per GPU, as the node agent
     runs them; host-resource tests still take turns under their lock).  A device whose run raised reports it
-    as a failed ``run`` test instead of losing the other devices' results."""
+    as a failed ``run`` test instead of losing the other devices' results.  ``extra``: as :func:`run`'s."""
+    more = {"extra": tuple(extra)} if extra else {}  # none: the call run() has always got
     out: Dict[int, Dict[str, Dict[str, Any]]] = {}
     missing: List[NativeUnavailable] = []  # no library at all: raised in the caller's thread, not per device
 
     def one(d: int) -> None:
         try:
-            out[d] = run(level, d)
+            out[d] = run(level, d, **more)
         except NativeUnavailable as e:
             missing.append(e)
         except Exception as e:  # a broken device: a failed test, not a lost report
@@ -1404,12 +1423,12 @@ def fabric_tests(devices: List[int], p2p: bool = True, rccl: bool = True,
 
 
 def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
-            clock: Any = None, progress: Any = None) -> Dict[str, Any]:
+            clock: Any = None, progress: Any = None, extra: Sequence[str] = ()) -> Dict[str, Any]:
     """Acceptance burn-in: the per-device suite of ``level`` on every device, round after round, for
     ``minutes``.  Passes only if every round of every device passed; reports each rate per device as
     min / median / max over the rounds (a GPU that drifts or throttles under sustained load shows as a wide
     spread or a late failure), how many rounds each test passed only as degraded, and the first failing
-    rounds."""
+    rounds.  ``extra``: opt-in tests every round runs too, as :func:`run`'s."""
     import statistics
     import time as _time
     clock = clock or _time.monotonic
@@ -1422,7 +1441,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
     from ..models.peers import judge_node
     node_rounds: Dict[str, int] = {}  # rounds with a node-wide shortfall, per test.metric
     while True:
-        res = run_devices(level, devices, parallel)
+        res = run_devices(level, devices, parallel, **({"extra": tuple(extra)} if extra else {}))
         for f in judge_node(res):  # each round's GPUs against each other, as the agent judges them
             key = f"{f['test']}.{f['metric']}"
             node_rounds[key] = node_rounds.get(key, 0) + 1
@@ -1461,7 +1480,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--format json|text]``:
+    [--atomics] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1477,6 +1496,9 @@ def main(argv=None) -> int:
     ap.add_argument("--xgmi-kernel", dest="xgmi_kernel", action="store_true",
                     help="level 2: also load the xGMI links from a kernel (CU stores and loads) and say of every slow "
                          "copy whether the link or the copy engine was slow")
+    ap.add_argument("--atomics", action="store_true",
+                    help="also run the atomics diagnostic on every device: atomic adds, max, xor and returning adds "
+                         "from every XCD onto one array, every element checked (ops/atomics.py)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1490,10 +1512,11 @@ def main(argv=None) -> int:
                                                                                 "error": msg}, indent=1))
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
+    more = {"extra": ("atomics",)} if args.atomics else {}  # likewise run_devices and burn_in
     if args.duration > 0:
         import sys as _sys
         b = burn_in(args.level, devices, args.duration, max(1, args.parallel),
-                    progress=lambda line: print(line, file=_sys.stderr, flush=True))
+                    progress=lambda line: print(line, file=_sys.stderr, flush=True), **more)
         if args.level >= 2 and (args.p2p or args.rccl):  # the node-level tests once, after the rounds
             b["fabric"] = fabric_tests(devices, args.p2p, args.rccl, args.timeout or None, **xk)
             b["pass"] = b["pass"] and all(r.get("pass") for r in b["fabric"].values())
@@ -1517,7 +1540,7 @@ def main(argv=None) -> int:
         else:
             print(json.dumps(b, indent=1))
         return 0 if b["pass"] else 1
-    results = run_devices(args.level, devices, max(1, args.parallel))
+    results = run_devices(args.level, devices, max(1, args.parallel), **more)
     from ..models.peers import finding_text, judge_node
     findings = judge_node(results)  # GPUs measured together: each against the others (lone: the references)
     out: Dict[str, Any] = {"devices": {d: {"info": device_info(d), "tests": results[d]} for d in devices}}

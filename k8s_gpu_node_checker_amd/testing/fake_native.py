@@ -1,4 +1,5 @@
-"""CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so`` and ``libmi355x_fabric.so``.
+"""CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so`` and
+``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -511,6 +512,73 @@ class FakeXgmiLib:
         return 0
 
 
+def atomics_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeAtomicsLib` stands in for, read from csrc/atomics/atomics.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "atomics", "atomics.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(atomics_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeAtomicsLib:
+    """``libmi355x_atomics.so`` for a node of ``n`` GPUs: every kind clean on all ``xcds`` XCDs.
+
+    wrong:    ``{(device, kind index): wrong elements}``; the first of them is element ``first_bad``, read back as
+              ``want ^ 0x100``
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``atomics{device}`` in ``calls``: empty = never called."""
+
+    KINDS = 8
+    WANT = 0x47800100
+
+    def __init__(self, n: int = 8, wrong: Optional[Dict[Tuple[int, int], int]] = None, first_bad: int = 0x690,
+                 xcds: int = 8, ms: float = 0.4, physical: Optional[int] = None):
+        self.n, self.wrong, self.first_bad, self.xcds, self.ms = n, dict(wrong or {}), first_bad, xcds, ms
+        self.physical = physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def atomics_last_error(self) -> bytes:
+        return self.err
+
+    def atomics_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def atomics_test(self, device, words, adders, kind_mask, seed, iters, inject_kind, inject_word, inject_drop_adder,
+                     errors, first_bad, got, want, want_without, ops, xcd_waves, ms):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"atomics{device}")
+        if not 0 <= device < self.n or words < 1 or not 1 <= adders <= 32 or iters < 1 or not kind_mask \
+                or kind_mask >> self.KINDS:
+            self.err = b"atomics test: need a valid device, words 1..2^31, adders 1..32, iters >= 1 and a mask of known kinds"
+            return -2
+        for k in range(self.KINDS):
+            on = bool((kind_mask >> k) & 1)
+            bad = self.wrong.get((device, k), 0) if on else 0
+            if on and k == inject_kind:
+                bad += 1
+            errors[k] = bad
+            first_bad[k] = (inject_word if k == inject_kind else self.first_bad) if bad else (1 << 64) - 1
+            want[k] = self.WANT if bad else 0
+            got[k] = self.WANT ^ 0x100 if bad else 0
+            want_without[k] = got[k] if k == inject_kind and inject_drop_adder >= 0 else 0
+            ops[k] = words * adders if on else 0
+            ms[k] = self.ms if on else 0.0
+            for x in range(8):
+                xcd_waves[8 * k + x] = max(1, -(-words // 64) * adders // self.xcds) if on and x < self.xcds else 0
+        return 0
+
+
 class FakeFabricLib:
     """``libmi355x_fabric.so`` (in-process RCCL communicator over the node's GPUs)."""
 
@@ -594,9 +662,11 @@ class NarrowedDiagLib:
         return on_physical
 
 
-def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, **diag_kw) -> None:
-    """Make this process's ``ops.diag``, ``ops.fabric`` and ``ops.xgmi`` use the fakes: ``FakeDiagLib(n, **diag_kw)``,
-    ``FakeFabricLib(**fabric)`` and ``FakeXgmiLib(n, **xgmi)``.  The node agent's diagnostic children run it first when the agent is given
+def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
+            **diag_kw) -> None:
+    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi`` and ``ops.atomics`` use the fakes:
+    ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)`` and
+    ``FakeAtomicsLib(n, **atomics)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
     child code path runs unchanged on CPU with scripted GPUs; a child narrowed to one GPU (``HIP_VISIBLE_DEVICES``)
     sees only that one, as under HIP."""
@@ -612,3 +682,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import xgmi as xgmi_mod
     xlib = FakeXgmiLib(n=n, **(xgmi or {}))
     xgmi_mod.lib = lambda: xlib
+    from ..ops import atomics as atomics_mod
+    alib = FakeAtomicsLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(atomics or {}))
+    atomics_mod.lib = lambda: alib
