@@ -8,13 +8,16 @@ artefact               source                                              toolc
 ``_fastpath*.so``      ``csrc/fastpath/fastpath.cpp`` (CPython ext)        g++ -O3
 ``libmi355x_probe.so`` ``csrc/probe/probe.cpp`` (C ABI over libamd_smi)     g++ + /opt/rocm/lib/libamd_smi
 ``mi355x-probe``       ``csrc/probe/probe_main.cpp`` (standalone CLI)       g++ + libamd_smi
-``libmi355x_diag.so``  ``csrc/diag/diag.hip`` (HIP kernels, gfx950 only)    hipcc --offload-arch=gfx950
+``libmi355x_diag.so``  ``csrc/diag/diag.hip`` + ``csrc/diag/*.h`` (kernels)   hipcc --offload-arch=gfx950
 ``libmi355x_xgmi.so``  ``csrc/xgmi/xgmi.hip`` (kernel-driven xGMI test)      hipcc --offload-arch=gfx950
 ``libmi355x_atomics.so`` ``csrc/atomics/atomics.hip`` (atomics diagnostic)      hipcc --offload-arch=gfx950
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
-Outputs are rebuilt only when a source is newer or the build command changed (``--force`` to override).
+The four HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``).
+Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
+
+Outputs are rebuilt only when a source or header is newer or the build command changed (``--force`` to override).
 No JIT cache, nothing outside the tree: the ``.so`` files travel with the
 source snapshot to the GPU box.
 """
@@ -46,6 +49,9 @@ def _targets() -> Dict[str, Dict[str, object]]:
     hipcc = os.path.join(ROCM, "bin", "hipcc")
     smi = ["-I", os.path.join(ROCM, "include"), "-L", os.path.join(ROCM, "lib"), "-lamd_smi",
            f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"]
+    # every HIP library is built by the same line (fabric adds RCCL after its sources); includes are relative, no -I
+    hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
+    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all four share
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -72,32 +78,32 @@ def _targets() -> Dict[str, Dict[str, object]]:
         },
         "diag": {
             "sources": [os.path.join(CSRC, "diag", "diag.hip")],
-            "headers": [os.path.join(CSRC, "diag", "v4_plan.h"), os.path.join(CSRC, "diag", "valu_ref.h")],
+            "headers": [os.path.join(CSRC, "diag", h) for h in (
+                "types.h", "gemm_kernels.h", "v4_plan.h", "gemm_check.h", "mem_kernels.h", "burn_kernels.h",
+                "valu_ref.h", "xcd_kernels.h", "gemm_host.h")] + [hip_host],
             "out": os.path.join(OUT, "libmi355x_diag.so"),
-            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-                    "-Wall", "-Wno-unused-result"],
+            "cmd": hip_cmd,
             "requires": hipcc,
         },
-        "xgmi": {  # the diag target's line: plain HIP, no RCCL
+        "xgmi": {
             "sources": [os.path.join(CSRC, "xgmi", "xgmi.hip")],
+            "headers": [hip_host],
             "out": os.path.join(OUT, "libmi355x_xgmi.so"),
-            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-                    "-Wall", "-Wno-unused-result"],
+            "cmd": hip_cmd,
             "requires": hipcc,
         },
-        "atomics": {  # the xgmi target's line
+        "atomics": {
             "sources": [os.path.join(CSRC, "atomics", "atomics.hip")],
-            "headers": [os.path.join(CSRC, "atomics", "atomics_ref.h")],
+            "headers": [os.path.join(CSRC, "atomics", "atomics_ref.h"), hip_host],
             "out": os.path.join(OUT, "libmi355x_atomics.so"),
-            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-                    "-Wall", "-Wno-unused-result"],
+            "cmd": hip_cmd,
             "requires": hipcc,
         },
         "fabric": {
             "sources": [os.path.join(CSRC, "fabric", "fabric.hip")],
+            "headers": [hip_host],
             "out": os.path.join(OUT, "libmi355x_fabric.so"),
-            "cmd": [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-                    "-Wall", "-Wno-unused-result"],
+            "cmd": hip_cmd,
             "post": ["-L", os.path.join(ROCM, "lib"), "-lrccl", f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"],
             "requires": hipcc,
         },

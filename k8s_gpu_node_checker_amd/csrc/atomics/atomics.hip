@@ -15,31 +15,17 @@
 //            wave-instruction covers 64 consecutive elements (256 contiguous bytes, 512 for the 64-bit kinds)
 //   verify   plain loads; each element is held against atomics_expected() (atomics_ref.h), bit for bit: wrong
 //            elements are counted and the lowest wrong index kept
-// It carries its own copies of the few host helpers it shares with diag.hip and xgmi.hip (DevBuf, Timer): their C
-// ABIs are pinned by the tests and stay untouched.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <string>
 
+#include "../common/hip_host.h"
 #include "atomics_ref.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-#define ATOMICS_CHECK(expr)                                                               \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      (void)hipGetLastError(); /* a failed allocation must not fail the next call's check */ \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-      return -1;                                                                          \
-    }                                                                                     \
-  } while (0)
 
 constexpr unsigned THREADS = 256;
 constexpr int XCDS = 8;
@@ -181,15 +167,6 @@ __global__ void __launch_bounds__(THREADS) ticket_verify_kernel(const unsigned i
   }
 }
 
-int cu_count(int device) {
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
-    (void)hipGetLastError();
-    cus = 256;  // the MI355X's CU count (a grid size only: any value is correct, this one fills the chip)
-  }
-  return cus;
-}
-
 // grid of the grid-stride fill / verify kernels: 8 workgroups per CU, never more than one thread per element
 unsigned flat_grid(int cus, size_t n) {
   return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((n + THREADS - 1) / THREADS, static_cast<size_t>(cus) * 8)));
@@ -201,42 +178,9 @@ unsigned slice_count(int cus, size_t n, int adders) {
   return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((n + THREADS - 1) / THREADS, want)));
 }
 
-// Device allocation, freed on every return path.
-struct DevBuf {
-  void* ptr = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes); }
-  ~DevBuf() {
-    if (ptr) (void)hipFree(ptr);
-  }
-};
-
-// A pair of events, released on every return path.
-struct Timer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  Timer() = default;
-  Timer(const Timer&) = delete;
-  Timer& operator=(const Timer&) = delete;
-  hipError_t create() {
-    hipError_t e = hipEventCreate(&e0);
-    return e == hipSuccess ? hipEventCreate(&e1) : e;
-  }
-  ~Timer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
-// Self-check hook (as xgmi.hip's flip_word): bit 4 of the element's low 32-bit word is flipped from the host.
+// Self-check hook: bit 4 of the element's low 32-bit word is flipped from the host (the entry point checks the range).
 int flip_element(void* buf, size_t elem, int elem_bytes) {
-  uint32_t* w = reinterpret_cast<uint32_t*>(static_cast<char*>(buf) + elem * static_cast<size_t>(elem_bytes));
-  uint32_t v = 0;
-  ATOMICS_CHECK(hipMemcpy(&v, w, sizeof v, hipMemcpyDeviceToHost));
-  v ^= 0x10u;
-  ATOMICS_CHECK(hipMemcpy(w, &v, sizeof v, hipMemcpyHostToDevice));
-  return 0;
+  return flip_word_bit(reinterpret_cast<uint32_t*>(static_cast<char*>(buf) + elem * static_cast<size_t>(elem_bytes)));
 }
 
 struct Launch {
@@ -309,14 +253,7 @@ extern "C" {
 
 const char* atomics_last_error(void) { return g_err.c_str(); }
 
-int atomics_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n;
-}
+int atomics_device_count(void) { return device_count(); }
 
 // Every kind whose bit is set in `kind_mask` (bit k: AtomicsKind k of atomics_ref.h), one after the other, on
 // `words` elements with `adders` operations each.  Per kind: `iters` iterations of fill, atomics, verify; only the
@@ -344,7 +281,7 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
                  unsigned long long* first_bad, unsigned long long* got, unsigned long long* want,
                  unsigned long long* want_without, unsigned long long* ops, unsigned long long* xcd_waves, double* ms) {
   int n = 0;
-  ATOMICS_CHECK(hipGetDeviceCount(&n));
+  HIP_CHECK(hipGetDeviceCount(&n));
   if (device < 0 || device >= n || words < 1 || words > MAX_WORDS || adders < 1 || adders > ATOMICS_MAX_ADDERS ||
       iters < 1 || !kind_mask || (kind_mask >> ATOMICS_KINDS)) {
     g_err = "atomics test: need a valid device, words 1..2^31, adders 1..32 (the float kinds' sums are exact up to "
@@ -371,17 +308,17 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
     for (int x = 0; x < XCDS; ++x) xcd_waves[XCDS * k + x] = 0;
   }
   int cur = 0;
-  ATOMICS_CHECK(hipGetDevice(&cur));
-  ATOMICS_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDevice(&cur));
+  HIP_CHECK(hipSetDevice(device));
   const int cus = cu_count(device);
   DevBuf buf, stats;
   const size_t array_bytes = (kind_mask & ~(1u << ATOMICS_TICKET)) ? words * 8 : 0;  // the widest kind's
   const size_t ticket_bytes = ((kind_mask >> ATOMICS_TICKET) & 1u) ? plan.elements() * sizeof(unsigned int) : 0;
-  ATOMICS_CHECK(buf.alloc(std::max(array_bytes, ticket_bytes)));
-  ATOMICS_CHECK(stats.alloc(2 * sizeof(Stats)));  // [0] the atomics launch's, [1] the verify launch's
+  HIP_CHECK(buf.alloc(device, std::max(array_bytes, ticket_bytes)));
+  HIP_CHECK(stats.alloc(device, 2 * sizeof(Stats)));  // [0] the atomics launch's, [1] the verify launch's
   Stats* dst = static_cast<Stats*>(stats.ptr);
   Timer tm;
-  ATOMICS_CHECK(tm.create());
+  HIP_CHECK(tm.create());
   Stats zero[2] = {};
   zero[0].first_bad = zero[1].first_bad = ~0ULL;
   for (int k = 0; k < ATOMICS_KINDS; ++k) {
@@ -393,25 +330,25 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
       const bool hooked = k == inject_kind && it == iters - 1;
       const bool drop = hooked && inject_drop_adder >= 0;
       Launch l = {buf.ptr, words, adders, kseed + static_cast<uint64_t>(it), cus, dst};
-      ATOMICS_CHECK(hipMemcpy(dst, zero, sizeof zero, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dst, zero, sizeof zero, hipMemcpyHostToDevice));
       launch(k, 0, l, -1, -1);
-      ATOMICS_CHECK(hipGetLastError());
-      ATOMICS_CHECK(hipEventRecord(tm.e0, nullptr));
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(tm.e0, nullptr));
       launch(k, 1, l, drop ? inject_word : -1, drop ? inject_drop_adder : -1);
-      ATOMICS_CHECK(hipGetLastError());
-      ATOMICS_CHECK(hipEventRecord(tm.e1, nullptr));
-      ATOMICS_CHECK(hipEventSynchronize(tm.e1));
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(tm.e1, nullptr));
+      HIP_CHECK(hipEventSynchronize(tm.e1));
       if (hooked && !drop)
         if (const int rc = flip_element(buf.ptr, static_cast<size_t>(inject_word), elem_bytes)) return rc;
       l.st = dst + 1;
       launch(k, 2, l, -1, -1);
-      ATOMICS_CHECK(hipGetLastError());
-      ATOMICS_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipDeviceSynchronize());
       float t = 0.f;
-      ATOMICS_CHECK(hipEventElapsedTime(&t, tm.e0, tm.e1));
+      HIP_CHECK(hipEventElapsedTime(&t, tm.e0, tm.e1));
       total_ms += t;
       Stats h[2];
-      ATOMICS_CHECK(hipMemcpy(h, dst, sizeof h, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(h, dst, sizeof h, hipMemcpyDeviceToHost));
       errors[k] += h[0].errors + h[1].errors;  // [0]: tickets returned out of range
       ops[k] = h[0].ops;
       for (int x = 0; x < XCDS; ++x) xcd_waves[XCDS * k + x] = h[0].waves[x];
@@ -419,7 +356,7 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
         const uint64_t e = h[1].first_bad;
         first_bad[k] = e;
         unsigned long long g = 0;
-        ATOMICS_CHECK(hipMemcpy(&g, static_cast<char*>(buf.ptr) + e * static_cast<size_t>(elem_bytes),
+        HIP_CHECK(hipMemcpy(&g, static_cast<char*>(buf.ptr) + e * static_cast<size_t>(elem_bytes),
                                 static_cast<size_t>(elem_bytes), hipMemcpyDeviceToHost));
         got[k] = g;
         want[k] = k == ATOMICS_TICKET ? atomics_ticket_expected(plan, e, adders) : atomics_expected(k, e, adders, l.seed);
@@ -429,7 +366,7 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
     }
     ms[k] = total_ms / iters;
   }
-  ATOMICS_CHECK(hipSetDevice(cur));
+  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

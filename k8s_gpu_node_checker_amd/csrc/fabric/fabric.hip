@@ -33,9 +33,9 @@
 
 #include <unistd.h>
 
-namespace {
+#include "../common/hip_host.h"  // g_err and HIP_CHECK; the deadline and device state here are RCCL's own
 
-thread_local std::string g_err;
+namespace {
 
 // RCCL prints its version banner on stdout during communicator init; callers (mi355x-diag, the
 // fabric CLI) write JSON there, so the banner is sent to stderr instead while the scope lives.
@@ -57,16 +57,6 @@ struct StdoutToStderr {
     }
   }
 };
-
-#define HIP_OK(expr)                                                          \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      (void)hipGetLastError(); /* not left for the next call's check */      \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-      return -1;                                                              \
-    }                                                                         \
-  } while (0)
 
 #define NCCL_OK(expr)                                                         \
   do {                                                                        \
@@ -170,13 +160,13 @@ unsigned grid_for(size_t n) { return static_cast<unsigned>(std::min<size_t>((n +
 
 int ensure_buffers(Dev& d, size_t bytes) {
   if (d.cap >= bytes) return 0;
-  HIP_OK(hipSetDevice(d.device));
-  if (d.in) HIP_OK(hipFree(d.in));
-  if (d.out) HIP_OK(hipFree(d.out));
+  HIP_CHECK(hipSetDevice(d.device));
+  if (d.in) HIP_CHECK(hipFree(d.in));
+  if (d.out) HIP_CHECK(hipFree(d.out));
   d.in = d.out = nullptr;
   d.cap = 0;
-  HIP_OK(hipMalloc(&d.in, bytes));
-  HIP_OK(hipMalloc(&d.out, bytes));
+  HIP_CHECK(hipMalloc(&d.in, bytes));
+  HIP_CHECK(hipMalloc(&d.out, bytes));
   d.cap = bytes;
   return 0;
 }
@@ -232,7 +222,7 @@ int sync_all(Ctx& c, const Deadline& dl, const char* what) {
   for (;;) {
     bool busy = false;
     for (Dev& d : c.devs) {
-      HIP_OK(hipSetDevice(d.device));
+      HIP_CHECK(hipSetDevice(d.device));
       hipError_t e = hipStreamQuery(d.stream);
       if (e == hipErrorNotReady) {
         (void)hipGetLastError();
@@ -365,13 +355,13 @@ int fabric_run(void* ctx, int op, size_t bytes, int iters, int warmup, double* o
 
   for (int r = 0; r < n; ++r) {  // rank-coded inputs (see the header)
     Dev& d = c.devs[static_cast<size_t>(r)];
-    HIP_OK(hipSetDevice(d.device));
+    HIP_CHECK(hipSetDevice(d.device));
     float a = 0.f, b = static_cast<float>(r + 1);
     size_t chunk = in_n;
     if (op == REDUCE_SCATTER) { a = static_cast<float>(r + 1); b = static_cast<float>(r + 1); chunk = per; }
     if (op == ALL_TO_ALL) { a = 1.f; b = static_cast<float>(r * n); chunk = per; }
     hipLaunchKernelGGL(fill_kernel, dim3(grid_for(in_n)), dim3(256), 0, d.stream, d.in, in_n, chunk, a, b);
-    HIP_OK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
   }
   if (int rc = sync_all(c, dl, "input fill"); rc != 0) return rc;
 
@@ -392,15 +382,15 @@ int fabric_run(void* ctx, int op, size_t bytes, int iters, int warmup, double* o
 
   // one more call on freshly zeroed outputs, then every element checked on its GPU
   for (Dev& d : c.devs) {
-    HIP_OK(hipSetDevice(d.device));
-    HIP_OK(hipMemsetAsync(d.out, 0, out_n * sizeof(float), d.stream));
-    HIP_OK(hipMemsetAsync(d.errors, 0, sizeof(unsigned long long), d.stream));
+    HIP_CHECK(hipSetDevice(d.device));
+    HIP_CHECK(hipMemsetAsync(d.out, 0, out_n * sizeof(float), d.stream));
+    HIP_CHECK(hipMemsetAsync(d.errors, 0, sizeof(unsigned long long), d.stream));
   }
   if (int rc = issue(c, op, count, dl); rc != 0) return rc;
   const float tri = static_cast<float>(n) * static_cast<float>(n + 1) / 2.f;
   for (int r = 0; r < n; ++r) {
     Dev& d = c.devs[static_cast<size_t>(r)];
-    HIP_OK(hipSetDevice(d.device));
+    HIP_CHECK(hipSetDevice(d.device));
     float a = 0.f, b = tri;
     size_t chunk = out_n;
     if (op == REDUCE_SCATTER) b = static_cast<float>(r + 1) * tri;
@@ -408,14 +398,14 @@ int fabric_run(void* ctx, int op, size_t bytes, int iters, int warmup, double* o
     if (op == ALL_TO_ALL) { a = static_cast<float>(n); b = static_cast<float>(r); chunk = per; }
     hipLaunchKernelGGL(verify_kernel, dim3(grid_for(out_n)), dim3(256), 0, d.stream, d.out, out_n, chunk, a, b,
                        d.errors);
-    HIP_OK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
   }
   if (int rc = sync_all(c, dl, "verified collective"); rc != 0) return rc;
   unsigned long long bad = 0;
   for (Dev& d : c.devs) {
     unsigned long long e = 0;
-    HIP_OK(hipSetDevice(d.device));
-    HIP_OK(hipMemcpy(&e, d.errors, sizeof(e), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipSetDevice(d.device));
+    HIP_CHECK(hipMemcpy(&e, d.errors, sizeof(e), hipMemcpyDeviceToHost));
     bad += e;
   }
   const double moved = static_cast<double>(count * sizeof(float));  // the larger per-rank buffer

@@ -6,33 +6,16 @@
 // writes into (or reads from) a buffer on each of its peers from a kernel, verifies every byte, and times each
 // destination with the wall clock.  ops/xgmi.py is its Python side; ops/diag.p2p_matrix(kernel=True) sets its
 // rates next to the copy path's to tell a link from an engine.
-//
-// It carries its own copies of the few host helpers it shares with diag.hip (DevBuf, Timer, PollDeadline,
-// wait_event_polled, event_ms, enable_peer, mix32, pattern): diag.hip's C ABI is pinned by the tests and stays
-// untouched.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
-#include <string>
-#include <thread>
+
+#include "../common/hip_host.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-#define XGMI_CHECK(expr)                                                                  \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      (void)hipGetLastError(); /* a failed allocation must not fail the next call's check */ \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-      return -1;                                                                          \
-    }                                                                                     \
-  } while (0)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // native 16-byte vector (one dwordx4 access)
 
@@ -42,15 +25,6 @@ constexpr unsigned U = 8;         // independent 16-byte accesses in flight per 
 constexpr size_t CHUNK = static_cast<size_t>(U) * THREADS;  // elements one workgroup moves per step: 32 KiB
 constexpr int XCDS = 8;
 constexpr int SLOT_WORDS = 4;     // per destination: first start, last end, bad elements, lowest bad element
-
-__device__ __forceinline__ uint32_t mix32(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return static_cast<uint32_t>(x);
-}
 
 // the address-hash pattern of the memtest and the copy-path pair test: element i holds four hashed words
 __device__ __forceinline__ u32x4 pattern(size_t i, uint64_t seed) {
@@ -186,110 +160,13 @@ __global__ void __launch_bounds__(THREADS) verify_kernel(const u32x4* p, size_t 
   }
 }
 
-int cu_count(int device) {
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
-    (void)hipGetLastError();
-    cus = 256;  // the MI355X's CU count (a grid size only: any value is correct, this one fills the chip)
-  }
-  return cus;
-}
-
 // grid of the grid-stride fill / verify kernels: 4 workgroups per CU, never more than one thread per element
 unsigned flat_grid(int device, size_t n) {
   return static_cast<unsigned>(std::min<size_t>((n + THREADS - 1) / THREADS, static_cast<size_t>(cu_count(device)) * 4));
 }
 
-hipError_t event_ms(hipEvent_t a, hipEvent_t b, float* ms) {
-  *ms = 0.f;
-  return hipEventElapsedTime(ms, a, b);
-}
-
-// Device allocation owned by its device (frees with that device current).
-struct DevBuf {
-  int device = -1;
-  void* ptr = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  hipError_t alloc(int dev, size_t bytes) {
-    device = dev;
-    hipError_t e = hipSetDevice(dev);
-    return e != hipSuccess ? e : hipMalloc(&ptr, bytes);
-  }
-  ~DevBuf() {
-    if (ptr) {
-      int cur = 0;
-      if (hipGetDevice(&cur) == hipSuccess && hipSetDevice(device) == hipSuccess) {
-        (void)hipFree(ptr);
-        (void)hipSetDevice(cur);
-      }
-    }
-  }
-};
-
-// A pair of events and an optional stream, released on every return path.
-struct Timer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t stream = nullptr;
-  Timer() = default;
-  Timer(const Timer&) = delete;
-  Timer& operator=(const Timer&) = delete;
-  hipError_t create(bool own_stream = false) {
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess && own_stream) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    return e;
-  }
-  ~Timer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-hipError_t enable_peer(int from, int to) {
-  hipError_t e = hipSetDevice(from);
-  if (e != hipSuccess) return e;
-  e = hipDeviceEnablePeerAccess(to, 0);
-  if (e == hipErrorPeerAccessAlreadyEnabled) {
-    (void)hipGetLastError();  // sticky-free: clear it
-    return hipSuccess;
-  }
-  return e;
-}
-
-// Polled completion with a deadline: a hung link must not block the caller.
-using SteadyClock = std::chrono::steady_clock;
-struct PollDeadline {
-  double limit_ms;
-  SteadyClock::time_point t0 = SteadyClock::now();
-  explicit PollDeadline(double ms) : limit_ms(ms) {}
-  bool bounded() const { return limit_ms > 0.0; }
-  bool passed() const {
-    return bounded() && std::chrono::duration<double, std::milli>(SteadyClock::now() - t0).count() >= limit_ms;
-  }
-};
-// hipSuccess once `ev` completed, hipErrorNotReady when the deadline passed first, else the query's error.
-hipError_t wait_event_polled(hipEvent_t ev, const PollDeadline& dl) {
-  if (!dl.bounded()) return hipEventSynchronize(ev);
-  for (;;) {
-    hipError_t q = hipEventQuery(ev);
-    if (q != hipErrorNotReady) return q;
-    if (dl.passed()) return hipErrorNotReady;
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-  }
-}
-
-// Self-check hook (as diag.hip's flip_slice_word): one bit of 32-bit word `word` of `buf` is flipped from the host.
-int flip_word(void* buf, long long word) {
-  uint32_t* w = static_cast<uint32_t*>(buf) + word;
-  uint32_t v = 0;
-  XGMI_CHECK(hipMemcpy(&v, w, sizeof v, hipMemcpyDeviceToHost));
-  v ^= 0x10u;
-  XGMI_CHECK(hipMemcpy(w, &v, sizeof v, hipMemcpyHostToDevice));
-  return 0;
-}
+// Self-check hook: one bit of 32-bit word `word` of `buf` is flipped from the host (the entry point checks the range).
+int flip_word(void* buf, long long word) { return flip_word_bit(static_cast<uint32_t*>(buf) + word); }
 
 }  // namespace
 
@@ -297,14 +174,7 @@ extern "C" {
 
 const char* xgmi_last_error(void) { return g_err.c_str(); }
 
-int xgmi_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n;
-}
+int xgmi_device_count(void) { return device_count(); }
 
 // `src` stores to (mode 0) or loads from (mode 1) a buffer of `bytes` (rounded down to 16) on every one of the
 // `ndst` devices in `dsts`, all from ONE kernel launch per iteration on `src` (fan_kernel): ndst = 1 is the pair
@@ -337,7 +207,7 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
                     int inject_dst, long long inject_word, double* gbps, unsigned long long* errors,
                     unsigned long long* first_bad, int* peer, double* total_gbps) {
   int n = 0;
-  XGMI_CHECK(hipGetDeviceCount(&n));
+  HIP_CHECK(hipGetDeviceCount(&n));
   if (src < 0 || src >= n || ndst < 1 || ndst > kMaxFan || iters < 1 || bytes < 16 || (mode != 0 && mode != 1)) {
     g_err = "xgmi kernel fan: need a valid source, 1..64 destinations, iters >= 1, bytes >= 16, mode 0 or 1";
     return -2;
@@ -354,7 +224,7 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
     return -2;
   }
   int cur = 0;
-  XGMI_CHECK(hipGetDevice(&cur));
+  HIP_CHECK(hipGetDevice(&cur));
   for (int i = 0; i < ndst; ++i) {
     errors[i] = 0;
     first_bad[i] = ~0ULL;
@@ -362,8 +232,8 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
     peer[i] = 1;
     if (dsts[i] == src) continue;
     int sd = 0, ds = 0;
-    XGMI_CHECK(hipDeviceCanAccessPeer(&sd, src, dsts[i]));
-    XGMI_CHECK(hipDeviceCanAccessPeer(&ds, dsts[i], src));
+    HIP_CHECK(hipDeviceCanAccessPeer(&sd, src, dsts[i]));
+    HIP_CHECK(hipDeviceCanAccessPeer(&ds, dsts[i], src));
     peer[i] = sd && ds;
     if (!peer[i]) {
       char msg[128];
@@ -372,8 +242,8 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
       g_err = msg;
       return -2;
     }
-    XGMI_CHECK(enable_peer(src, dsts[i]));
-    XGMI_CHECK(enable_peer(dsts[i], src));
+    HIP_CHECK(enable_peer(src, dsts[i]));
+    HIP_CHECK(enable_peer(dsts[i], src));
   }
   *total_gbps = 0.0;
   const uint64_t seed0 = 0x5A17C0DEULL + static_cast<uint64_t>(src) * 131;
@@ -385,31 +255,31 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
   FanArgs args = {};
   const unsigned long long cnt_init[2] = {0ULL, ~0ULL};
   for (int i = 0; i < ndst; ++i) {
-    XGMI_CHECK(b[i].alloc(dsts[i], nbytes));
+    HIP_CHECK(b[i].alloc(dsts[i], nbytes));
     args.buf[i] = static_cast<u32x4*>(b[i].ptr);
     if (mode == 0) {
-      XGMI_CHECK(cnt[i].alloc(dsts[i], sizeof cnt_init));
-      XGMI_CHECK(hipMemcpy(cnt[i].ptr, cnt_init, sizeof cnt_init, hipMemcpyHostToDevice));
-      XGMI_CHECK(hipMemset(b[i].ptr, 0xA5, nbytes));
+      HIP_CHECK(cnt[i].alloc(dsts[i], sizeof cnt_init));
+      HIP_CHECK(hipMemcpy(cnt[i].ptr, cnt_init, sizeof cnt_init, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemset(b[i].ptr, 0xA5, nbytes));
     } else {
       hipLaunchKernelGGL(fill_kernel, dim3(flat_grid(dsts[i], nvec)), dim3(THREADS), 0, nullptr, args.buf[i], nvec,
                          dst_seed(iter_seed(0), i));
-      XGMI_CHECK(hipGetLastError());
+      HIP_CHECK(hipGetLastError());
     }
-    XGMI_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipDeviceSynchronize());
   }
   if (mode == 1 && inject_dst >= 0) {
-    XGMI_CHECK(hipSetDevice(dsts[inject_dst]));
+    HIP_CHECK(hipSetDevice(dsts[inject_dst]));
     if (const int rc = flip_word(b[inject_dst].ptr, inject_word)) return rc;
   }
   // slots in src-local memory: [0] the warm-up's (discarded), [1] the timed launches'
-  XGMI_CHECK(hipSetDevice(src));
+  HIP_CHECK(hipSetDevice(src));
   unsigned long long slot_init[2][kMaxFan][SLOT_WORDS];
   for (auto& set : slot_init)
     for (auto& s : set) s[0] = ~0ULL, s[1] = 0ULL, s[2] = 0ULL, s[3] = ~0ULL;
-  XGMI_CHECK(slots.alloc(src, sizeof slot_init));
-  XGMI_CHECK(hipMemcpy(slots.ptr, slot_init, sizeof slot_init, hipMemcpyHostToDevice));
-  XGMI_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(slots.alloc(src, sizeof slot_init));
+  HIP_CHECK(hipMemcpy(slots.ptr, slot_init, sizeof slot_init, hipMemcpyHostToDevice));
+  HIP_CHECK(hipDeviceSynchronize());
   int clock_khz = 0;  // the wall clock's rate: 100 MHz on the MI355X
   if (hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, src) != hipSuccess || clock_khz <= 0) {
     (void)hipGetLastError();
@@ -419,7 +289,7 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
   const unsigned groups = std::max(1u, static_cast<unsigned>(cu_count(src)) * 4u / (XCDS * static_cast<unsigned>(ndst)));
   const dim3 grid(XCDS * static_cast<unsigned>(ndst) * groups);
   Timer tm;
-  XGMI_CHECK(tm.create(true));
+  HIP_CHECK(tm.create(true));
   unsigned long long* warm = static_cast<unsigned long long*>(slots.ptr);
   unsigned long long* timed = warm + kMaxFan * SLOT_WORDS;
   auto launch = [&](int it, unsigned long long* sl) {
@@ -429,11 +299,11 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
       hipLaunchKernelGGL(fan_kernel<1>, grid, dim3(THREADS), 0, tm.stream, args, ndst, groups, nvec, iter_seed(it), sl);
   };
   launch(-1, warm);
-  XGMI_CHECK(hipGetLastError());
-  XGMI_CHECK(hipEventRecord(tm.e0, tm.stream));
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(tm.e0, tm.stream));
   for (int it = 0; it < iters; ++it) launch(it, timed);
-  XGMI_CHECK(hipGetLastError());
-  XGMI_CHECK(hipEventRecord(tm.e1, tm.stream));
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(tm.e1, tm.stream));
   const PollDeadline dl(timeout_ms);
   Timer verify[kMaxFan];
   auto hung = [&](int i, const char* stage) {
@@ -454,12 +324,12 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
   };
   hipError_t w = wait_event_polled(tm.e1, dl);
   if (w == hipErrorNotReady) return hung(0, "the launches");  // one kernel for all: no destination to single out
-  XGMI_CHECK(w);
+  HIP_CHECK(w);
   float ms = 0.f;
-  XGMI_CHECK(event_ms(tm.e0, tm.e1, &ms));
+  HIP_CHECK(event_ms(tm.e0, tm.e1, &ms));
   *total_gbps = ms > 0.f ? static_cast<double>(ndst) * iters * static_cast<double>(nbytes) / (ms * 1e-3) / 1e9 : 0.0;
   unsigned long long got[kMaxFan][SLOT_WORDS];
-  XGMI_CHECK(hipMemcpy(got, timed, sizeof got, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(got, timed, sizeof got, hipMemcpyDeviceToHost));
   for (int i = 0; i < ndst; ++i) {
     // a window shorter than one tick of the clock counts as one tick
     const unsigned long long ticks = got[i][1] > got[i][0] ? got[i][1] - got[i][0] : 1ULL;
@@ -472,30 +342,30 @@ int xgmi_kernel_fan(int src, const int* dsts, int ndst, size_t bytes, int iters,
   }
   if (mode == 0) {
     if (inject_dst >= 0) {
-      XGMI_CHECK(hipSetDevice(dsts[inject_dst]));
+      HIP_CHECK(hipSetDevice(dsts[inject_dst]));
       if (const int rc = flip_word(b[inject_dst].ptr, inject_word)) return rc;
     }
     for (int i = 0; i < ndst; ++i) {
-      XGMI_CHECK(hipSetDevice(dsts[i]));
-      XGMI_CHECK(verify[i].create(false));
+      HIP_CHECK(hipSetDevice(dsts[i]));
+      HIP_CHECK(verify[i].create(false));
       unsigned long long* c = static_cast<unsigned long long*>(cnt[i].ptr);
       hipLaunchKernelGGL(verify_kernel, dim3(flat_grid(dsts[i], nvec)), dim3(THREADS), 0, nullptr,
                          static_cast<const u32x4*>(b[i].ptr), nvec, dst_seed(iter_seed(iters - 1), i), c, c + 1);
-      XGMI_CHECK(hipGetLastError());
-      XGMI_CHECK(hipEventRecord(verify[i].e0, nullptr));
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(verify[i].e0, nullptr));
     }
     for (int i = 0; i < ndst; ++i) {
       w = wait_event_polled(verify[i].e0, dl);
       if (w == hipErrorNotReady) return hung(i, "verification");
-      XGMI_CHECK(w);
+      HIP_CHECK(w);
       unsigned long long h[2];
-      XGMI_CHECK(hipSetDevice(dsts[i]));
-      XGMI_CHECK(hipMemcpy(h, cnt[i].ptr, sizeof h, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipSetDevice(dsts[i]));
+      HIP_CHECK(hipMemcpy(h, cnt[i].ptr, sizeof h, hipMemcpyDeviceToHost));
       errors[i] = h[0];
       first_bad[i] = h[1];
     }
   }
-  XGMI_CHECK(hipSetDevice(cur));
+  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

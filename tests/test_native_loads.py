@@ -121,3 +121,38 @@ def test_diag_exports_match_their_ctypes_signatures(monkeypatch):
         pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)  # (c_char_p: diag_device_arch's buffer)
         for p, t in zip(params, fn.argtypes):
             assert ("*" in p) == (isinstance(t, type) and issubclass(t, pointers)), (name, p, t)
+
+
+def quoted_includes(path, seen=None):
+    """Every file reachable from `path` through ``#include "..."``, each resolved relative to the file that names it."""
+    import os
+    import re
+    seen = set() if seen is None else seen
+    with open(path) as f:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+            target = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+            if target not in seen:
+                seen.add(target)
+                quoted_includes(target, seen)
+    return seen
+
+
+def test_every_build_target_lists_the_headers_its_sources_reach():
+    """build._stale() rebuilds a library when a file of ``sources`` + ``headers`` is newer than it: a header missing
+    from the list would leave a stale .so after an edit, so every reachable one must be listed (and exist)."""
+    import os
+
+    from k8s_gpu_node_checker_amd import build
+    targets = build._targets()
+    assert {"diag", "xgmi", "atomics", "fabric"} <= set(targets)
+    for name, spec in targets.items():
+        listed = {os.path.normpath(p) for p in list(spec["sources"]) + list(spec.get("headers", []))}
+        assert all(os.path.exists(p) for p in listed), (name, sorted(p for p in listed if not os.path.exists(p)))
+        reached = set()
+        for src in spec["sources"]:
+            quoted_includes(os.path.normpath(src), reached)
+        assert reached <= listed, (name, sorted(reached - listed))
+    # the HIP libraries share their host helpers and one build line
+    hip = [targets[n] for n in ("diag", "xgmi", "atomics", "fabric")]
+    assert all(any(h.endswith(os.path.join("common", "hip_host.h")) for h in t["headers"]) for t in hip)
+    assert all(t["cmd"] == hip[0]["cmd"] and "-I" not in t["cmd"] for t in hip)
