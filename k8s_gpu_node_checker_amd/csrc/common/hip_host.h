@@ -161,4 +161,13 @@ __device__ __forceinline__ uint32_t mix32(uint64_t x) {
   return static_cast<uint32_t>(x);
 }
 
+// Physical location of the calling wave: XCD (XCC_ID), shader engine, shader array and CU (HW_ID), packed
+// as xcd<<7 | se<<5 | sh<<4 | cu -- one of WAVE_SLOTS slots; the CUs of one MI355X occupy 256 of them.
+constexpr int WAVE_SLOTS = 1024;
+__device__ __forceinline__ unsigned wave_slot() {
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_ID, all 32 bits
+  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID[3:0]
+  return ((xcc & 7u) << 7) | (((hw >> 13) & 3u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
+}
+
 }  // namespace

@@ -38,14 +38,8 @@ __device__ __forceinline__ floatx4 burn_mfma(const i32x8& a, const i32x8& b, flo
   }
 }
 
-// Physical location of the calling wave: XCD (XCC_ID), shader engine, shader array and CU (HW_ID), packed
-// as xcd<<7 | se<<5 | sh<<4 | cu -- one of BURN_SLOTS slots; the CUs of one MI355X occupy 256 of them.
-constexpr int BURN_SLOTS = 1024;
-__device__ __forceinline__ unsigned wave_slot() {
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_ID, all 32 bits
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID[3:0]
-  return ((xcc & 7u) << 7) | (((hw >> 13) & 3u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
-}
+// The burn-ins' per-CU maps are indexed by wave_slot() (common/hip_host.h): one of its WAVE_SLOTS slots.
+constexpr int BURN_SLOTS = WAVE_SLOTS;
 
 template <int KIND>
 __global__ void __launch_bounds__(256) mfma_burn_kernel(const i32x8* __restrict__ fa, const i32x8* __restrict__ fb,

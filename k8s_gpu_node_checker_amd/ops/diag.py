@@ -155,6 +155,7 @@ KERNEL_REVISION: Dict[str, str] = {
     "valu": "chains8x4-r1",      # 8 chains x 4 steps per iteration, 2 workgroups per CU
     "regfile": "v8-255+a0-255",  # no rate verdict: the stamp says which registers a clean result covered
     "atomics": "8kinds-lane-per-element-r1",  # no rate verdict either (ops/atomics.py): which kinds a clean result covered
+    "lanes": "39ops-chains4-r1",  # no rate verdict either (ops/lanes.py): which ops a clean result covered
 }
 
 
@@ -856,6 +857,14 @@ def atomics_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return atomics.atomics_test(device, **kw)
 
 
+def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in lanes diagnostic (``ops/lanes.lanes_test``, its own library): every lane-crossing instruction of a
+    wave (DPP, the permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane / readfirstlane) in chains that
+    every lane checks bit for bit against the host's model.  No level runs it; ``run(extra=("lanes",))`` does."""
+    from . import lanes  # lazily: only who asks for the test needs libmi355x_lanes.so
+    return lanes.lanes_test(device, **kw)
+
+
 def _xcd_slices(fn: str, name: str, device: int, slice_bytes: int, passes: int, blocks_per_cu: int, seed: int,
                 inject_xcd: int, inject_word: int, *more: Any) -> Tuple[float, int, List[int], Dict[str, Any], str]:
     """What :func:`l2_bandwidth` and :func:`hbm_xcd` share: the call (``more`` = further out-parameters of ``fn``) and
@@ -1158,8 +1167,10 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "memtest": ("memtest", {}), "mfma": ("mfma_burn", {}), "lds": ("lds_test", {}), "l2": ("l2_bandwidth", {}),
     "valu": ("valu_burn", {}), "regfile": ("regfile_test", {}), "host_link": ("host_link", {}),
     "atomics": ("atomics_test", {}),  # in no level: run(extra=("atomics",))
+    "lanes": ("lanes_test", {}),  # in no level: run(extra=("lanes",))
 }
-_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test"))  # error counts only: nothing to scale
+# error counts only: nothing to scale
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test"))
 
 
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
@@ -1222,7 +1233,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``),
     each treated as the level's own are.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
@@ -1293,6 +1304,11 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         rates = " · ".join(f"{k} {v.get('gbs', 0):.0f}" for k, v in kinds.items())
         return (f"{r.get('words', '?')} elements x {r.get('adders', '?')} adders from "
                 f"{'/'.join(map(str, xcds)) or '?'} XCDs, {r.get('errors', 0)} wrong; {rates} GB/s")
+    if test == "lanes":
+        rows = r.get("ops") or {}
+        rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
+        return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+                f"XCDs, {r.get('errors', 0)} wrong lanes; {r.get('ms', 0):.1f} ms, mean {rate:.0f} G crossings/s")
     if test == "regfile":
         return (f"{r.get('simds', '?')} SIMDs x {r.get('bytes_per_simd', 0) // 1024} KiB "
                 f"({r.get('regs_per_lane', '?')} registers), {r.get('errors', 0)} bad words")
@@ -1480,7 +1496,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--format json|text]``:
+    [--atomics] [--lanes] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1499,6 +1515,10 @@ def main(argv=None) -> int:
     ap.add_argument("--atomics", action="store_true",
                     help="also run the atomics diagnostic on every device: atomic adds, max, xor and returning adds "
                          "from every XCD onto one array, every element checked (ops/atomics.py)")
+    ap.add_argument("--lanes", action="store_true",
+                    help="also run the lanes diagnostic on every device: every lane-crossing instruction of a wave "
+                         "(DPP, permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane) checked bit for bit "
+                         "against the host's model, wrong lanes located to their SIMD (ops/lanes.py)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1512,7 +1532,8 @@ def main(argv=None) -> int:
                                                                                 "error": msg}, indent=1))
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
-    more = {"extra": ("atomics",)} if args.atomics else {}  # likewise run_devices and burn_in
+    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes)) if on)
+    more = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.duration > 0:
         import sys as _sys
         b = burn_in(args.level, devices, args.duration, max(1, args.parallel),
