@@ -37,8 +37,9 @@
 // function returns a negative code and diag_last_error() says what failed.
 //
 // This file holds the entry points (every extern "C" block) and the runners only they use.  The kernels are in
-// gemm_kernels.h, gemm_check.h, mem_kernels.h, burn_kernels.h and xcd_kernels.h, the GEMM launch dispatch in
-// gemm_host.h, the host helpers shared with the other libraries in ../common/hip_host.h.
+// gemm_kernels.h (gemm_common.h and gemm_v1.h to gemm_v4.h, one GEMM generation each, on tile_order.h and v4_plan.h),
+// gemm_check.h, mem_kernels.h, burn_kernels.h and xcd_kernels.h, the GEMM launch dispatch in gemm_host.h, the host
+// helpers shared with the other libraries in ../common/hip_host.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>

@@ -139,7 +139,7 @@ int launch_fp8_ck(const void* A, const void* Bt, __bf16* C, double* csum, int M,
                 : launch_v3_ck_fp8(A, Bt, C, csum, M, N, Kcols, stream);
 }
 
-// The diagnostic runs (diag_gemm_*_x) take the bf16-output kernel wherever the production v3 configuration
+// The diagnostic runs (diag_gemm_bf16 / diag_gemm_fp8 in diag.hip) take the bf16-output kernel wherever the production v3 configuration
 // would run (LDS-staged epilogue, global_load_lds staging); other knob settings keep fp32 C.  v4 has one
 // configuration, always LDS-staged: it always has the bf16 output.
 bool v3_ck_path() { return g_gemm_epilogue == 1 && !g_gemm_buffer_loads; }
@@ -180,27 +180,12 @@ bool gemm_fused(int dt, int M, int N) {
   return v >= 4 || (v == 3 && v3_ck_path());
 }
 
-// Output tiles of a launch and their blockIdx regrouping (the mapping at the top of every GEMM kernel).
+// Output tiles of a launch and the group_m of their blockIdx regrouping (tile_order.h, which also maps a tile back
+// to the XCD that computed it: tile_xcds).
 struct TileGeom {
   int rows, cols, group_m;
 };
 constexpr TileGeom kGeomV1{BM, BN, 8}, kGeomV3{V2_BM, V2_BN, 4};
-
-// The XCD that computed each tile: workgroup b is dispatched to XCD b % 8 and computes the tile the regrouping
-// gives it.
-std::vector<int> tile_xcds(int tiles_m, int tiles_n, int group_m) {
-  const int nwg = tiles_m * tiles_n, q = nwg / 8, r = nwg % 8;
-  std::vector<int> out(static_cast<size_t>(nwg), -1);
-  for (int b = 0; b < nwg; ++b) {
-    const int xcd = b % 8;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    const int first_m = bid / (group_m * tiles_n) * group_m;
-    const int gsize = std::min(tiles_m - first_m, group_m);
-    const int tm = first_m + (bid % (group_m * tiles_n)) % gsize, tn = (bid % (group_m * tiles_n)) / gsize;
-    out[static_cast<size_t>(tm) * tiles_n + tn] = xcd;
-  }
-  return out;
-}
 
 // Whole-output check of C = A . Bt^T (the ck_* kernels).  ck_out[0] bad tiles, [1] bad columns, [2..9] bad tiles
 // per XCD, [10] / [11] the first bad tile's (row, column) in tiles or -1; *max_err the worst |csum - ref| / mag.

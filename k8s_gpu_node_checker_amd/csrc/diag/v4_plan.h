@@ -1,5 +1,5 @@
-// Schedules of the four-wave v4 GEMM K loop (diag.hip gemm_v4_kernel) as compile-time plans, and the checks
-// every plan must pass.  Plain constexpr C++: diag.hip includes this inside its anonymous namespace, and
+// Schedules of the four-wave v4 GEMM K loop (gemm_v4.h gemm_v4_kernel) as compile-time plans, and the checks
+// every plan must pass.  Plain constexpr C++: gemm_v4.h includes this inside its anonymous namespace, and
 // tests/test_gemm_plans.py compiles it with the host compiler to show the checks reject broken plans.
 #ifndef K8S_GPU_NODE_CHECKER_AMD_V4_PLAN_H_
 #define K8S_GPU_NODE_CHECKER_AMD_V4_PLAN_H_

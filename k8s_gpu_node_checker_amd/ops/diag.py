@@ -169,11 +169,11 @@ def rate_revision(test: str) -> str:
     return hashlib.sha256(_json.dumps(doc, sort_keys=True).encode()).hexdigest()[:12]
 
 
-# Sampled errors.  The v4 / v3 kernels the diagnostics time write bf16 C (diag.hip OUT_BF16_CK): there the error is
+# Sampled errors.  The v4 / v3 kernels the diagnostics time write bf16 C (gemm_v3.h OUT_BF16_CK): there the error is
 # what lies beyond the output's own rounding (half a bf16 ulp), so the limits below hold for both outputs.
 GEMM_MAX_REL_ERR = 2e-3       # vs fp32 reference; bf16 inputs are exact in fp32, so ~1e-5 is typical
 GEMM_FP8_MAX_ERR = 4e-5       # |C - ref| / sum|a*b|: the MX MFMA's own accumulation error is <= 1.6e-5
-# whole-output tile checksums (diag.hip gemm_checksum): |column sum of a tile - fp64 reference| / sum|a*b| over
+# whole-output tile checksums (gemm_host.h gemm_checksum): |column sum of a tile - fp64 reference| / sum|a*b| over
 # the same outputs.  Healthy MI355X maxima (profiles/gemm_checksum_mi355x.jsonl, deterministic run to run): bf16
 # 2.3e-9, MX-fp8 5.4e-7, so 43x / 18x margins.  At 8192^3 bf16 a tile column's sum|a*b| is ~5.2e5, so one output
 # off by more than ~0.05 (a typical output is ~30) fails its tile.
@@ -369,7 +369,7 @@ GEMM_VARIANTS = {"auto": 0, "v1": 1, "v2": 2, "v3": 3, "v4": 4, "v4t": 5}
 def set_gemm_variant(variant: str = "auto") -> None:
     """Select the bf16 GEMM kernel: ``auto`` (v4 for 256-multiples that fill the chip, else v1),
     ``v1`` 128x128 register-staged, ``v2`` 256x256 LDS-DMA, ``v3`` 256x256 staggered LDS-DMA (8 waves),
-    ``v4`` 256x256 with 4 waves of 128x128 and the loop's instruction order written out (diag.hip
+    ``v4`` 256x256 with 4 waves of 128x128 and the loop's instruction order written out (gemm_v4.h
     ``gemm_v4_kernel``).  v2-v4 need M, N multiples of 256.  fp8 / fp4 GEMMs always run v3."""
     lib().diag_set_gemm_variant(GEMM_VARIANTS[variant])
 
@@ -388,7 +388,7 @@ def set_gemm_buffer_loads(buffer_loads: bool) -> None:
 
 
 def set_gemm_schedule(schedule: int) -> None:
-    """v3 kernels: the K-tile phase that issues each LDS-DMA restaging piece (``V3_PHASE`` in diag.hip):
+    """v3 kernels: the K-tile phase that issues each LDS-DMA restaging piece (``V3_PHASE`` in gemm_v3.h):
     1 (default) = 0/2/2/4 pieces over the four phases, 0 = the earlier 2/0/4/2 order, kept for A/B."""
     if schedule not in (0, 1):
         raise ValueError(f"gemm schedule must be 0 or 1, not {schedule!r}")
@@ -638,7 +638,7 @@ def memtest(device: int = 0, gib: float = 8.0, passes: int = 1, seed: int = 0x5E
 
 def slot_name(slot: int) -> str:
     """``xcd3/se1/cu5`` (``/sh1`` when the wave sat in shader array 1) of a burn-in CU slot
-    (``wave_slot()`` in csrc/diag/diag.hip: xcd<<7 | se<<5 | sh<<4 | cu)."""
+    (``wave_slot()`` in csrc/common/hip_host.h: xcd<<7 | se<<5 | sh<<4 | cu)."""
     sh = (slot >> 4) & 1
     return f"xcd{slot >> 7}/se{(slot >> 5) & 3}/cu{slot & 15}" + ("/sh1" if sh else "")
 
