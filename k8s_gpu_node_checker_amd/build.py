@@ -80,8 +80,8 @@ def _targets() -> Dict[str, Dict[str, object]]:
         "diag": {
             "sources": [os.path.join(CSRC, "diag", "diag.hip")],
             "headers": [os.path.join(CSRC, "diag", h) for h in (
-                "types.h", "tile_order.h", "gemm_kernels.h", "gemm_common.h", "gemm_v1.h", "gemm_v2.h", "gemm_v3.h",
-                "gemm_v4.h", "v4_plan.h", "gemm_check.h", "mem_kernels.h", "burn_kernels.h",
+                "types.h", "tile_order.h", "gemm_epilogue.h", "gemm_kernels.h", "gemm_common.h", "gemm_v1.h", "gemm_v2.h",
+                "gemm_v3.h", "gemm_v4.h", "v4_plan.h", "gemm_check.h", "mem_kernels.h", "burn_kernels.h",
                 "valu_ref.h", "xcd_kernels.h", "gemm_host.h")] + [hip_host],
             "out": os.path.join(OUT, "libmi355x_diag.so"),
             "cmd": hip_cmd,

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <cstdint>
+#include "gemm_epilogue.h"
 #include "tile_order.h"
 #include "types.h"
 

@@ -29,7 +29,12 @@ namespace {
     __builtin_amdgcn_sched_barrier(0); \
   } while (0)
 
-// One 16 KiB region of a stage: 16 LDS-DMA wave-instructions of 8 rows, 2 per wave.
+// One 16 KiB region of a stage: 16 LDS-DMA wave-instructions of 8 rows, 2 per wave.  Instruction g's first row:
+__device__ __forceinline__ int stg_row0(int region, int g) {
+  return region == 0 || region == 3 ? (g >> 3) * 128 + (region == 0 ? 0 : 64) + (g & 7) * 8
+                                    : (g >> 2) * 64 + (region == 1 ? 0 : 32) + (g & 3) * 8;
+}
+
 template <bool FP8>
 __device__ __forceinline__ void stg_region(unsigned char* lds_stage, const __bf16* __restrict__ A,
                                            const __bf16* __restrict__ Bt, int K, int kt, int region, int i, int wid,
@@ -37,8 +42,7 @@ __device__ __forceinline__ void stg_region(unsigned char* lds_stage, const __bf1
   const int rsub = lane >> 3, phys = lane & 7;
   const int g = wid * 2 + i;
   const bool is_a = region == 0 || region == 3;
-  const int row0 = is_a ? (g >> 3) * 128 + (region == 0 ? 0 : 64) + (g & 7) * 8
-                        : (g >> 2) * 64 + (region == 1 ? 0 : 32) + (g & 3) * 8;
+  const int row0 = stg_row0(region, g);
   const int row = row0 + rsub;
   const int c = phys ^ swz_row_xor(row, FP8);
   const __bf16* gp = (is_a ? A : Bt) + static_cast<size_t>(row) * K + kt * BK + c * 8;
@@ -66,8 +70,7 @@ __device__ __forceinline__ void stg_region_buf(unsigned char* lds_stage, const S
   const int rsub = lane >> 3, phys = lane & 7;
   const int g = wid * 2 + i;
   const bool is_a = region == 0 || region == 3;
-  const int row0 = is_a ? (g >> 3) * 128 + (region == 0 ? 0 : 64) + (g & 7) * 8
-                        : (g >> 2) * 64 + (region == 1 ? 0 : 32) + (g & 3) * 8;
+  const int row0 = stg_row0(region, g);
   const int row = row0 + rsub;
   const int c = phys ^ swz_row_xor(row, FP8);
   const int voff = (row * K + c * 8) * 2;
@@ -92,6 +95,15 @@ __device__ __forceinline__ void v2_fill_buf(unsigned char* lds_stage, const StgB
   }
 }
 
+// MFMAs are not memory operations, so IR passes may sink them past the next s_barrier into the
+// other group's slot; an empty volatile asm that reads and writes each result of a phase pins them there.
+__device__ __forceinline__ void pin_acc(floatx4 (&acc)[8][4], int m0, int n0) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n) asm volatile("" : "+v"(acc[m0 + m][n0 + n]));
+}
+
 __device__ __forceinline__ void stg_mfma(floatx4 (&acc)[8][4], const bf16x8 (&af)[4][2], const bf16x8 (&bf)[2][2],
                                          int m0, int n0) {
 #pragma unroll
@@ -101,15 +113,13 @@ __device__ __forceinline__ void stg_mfma(floatx4 (&acc)[8][4], const bf16x8 (&af
 #pragma unroll
       for (int n = 0; n < 2; ++n)
         acc[m0 + m][n0 + n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m][s], bf[n][s], acc[m0 + m][n0 + n], 0, 0, 0);
-  // MFMAs are not memory operations, so IR passes may sink them past the next s_barrier into the
-  // other group's slot; an empty volatile asm that reads and writes each result pins them here.
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) asm volatile("" : "+v"(acc[m0 + m][n0 + n]));
+  pin_acc(acc, m0, n0);
 }
 
-// MX-fp8 (E4M3, unit E8M0 scales): one v_mfma_scale_f32_16x16x128_f8f6f4 covers the K-tile's 128 bytes.
+// MX-fp8 (E4M3, unit E8M0 scales): one v_mfma_scale_f32_16x16x128_f8f6f4 covers the K-tile's 128 bytes.  SCALE = 0
+// is the same K-tile on the unscaled instruction (zero scale operands select v_mfma_f32_16x16x128_f8f6f4): with unit
+// scales the two compute the same products, so the knob only changes which matrix-core path runs.
+template <int SCALE = 127>
 __device__ __forceinline__ void stg_mfma(floatx4 (&acc)[8][4], const i32x8 (&af)[4], const i32x8 (&bf)[2], int m0,
                                          int n0) {
 #pragma unroll
@@ -117,27 +127,8 @@ __device__ __forceinline__ void stg_mfma(floatx4 (&acc)[8][4], const i32x8 (&af)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
       acc[m0 + m][n0 + n] =
-          __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[m], bf[n], acc[m0 + m][n0 + n], 0, 0, 0, 127, 0, 127);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) asm volatile("" : "+v"(acc[m0 + m][n0 + n]));
-}
-
-// The same K-tile on the unscaled instruction (zero scale operands select v_mfma_f32_16x16x128_f8f6f4): with unit
-// scales the two compute the same products, so the knob only changes which matrix-core path runs.
-__device__ __forceinline__ void stg_mfma_unscaled(floatx4 (&acc)[8][4], const i32x8 (&af)[4], const i32x8 (&bf)[2],
-                                                  int m0, int n0) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-      acc[m0 + m][n0 + n] =
-          __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[m], bf[n], acc[m0 + m][n0 + n], 0, 0, 0, 0, 0, 0);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) asm volatile("" : "+v"(acc[m0 + m][n0 + n]));
+          __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[m], bf[n], acc[m0 + m][n0 + n], 0, 0, 0, SCALE, 0, SCALE);
+  pin_acc(acc, m0, n0);
 }
 
 // Fragment of one 16-row block: bf16 = two K=32 steps (chunks fq, fq+4); fp8 = the lane's 32
@@ -175,10 +166,7 @@ __device__ __forceinline__ void stg_mfma(floatx4 (&acc)[8][4], const u32x4 (&af)
         acc[m0 + m][n0 + n] =
             __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, acc[m0 + m][n0 + n], 4, 4, 0, 127, 0, 127);
       }
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) asm volatile("" : "+v"(acc[m0 + m][n0 + n]));
+  pin_acc(acc, m0, n0);
 }
 
 template <int DT>
@@ -197,7 +185,7 @@ struct StgFrags<DT_FP8U> {
 // One phase's MFMAs for the kernel's data type.
 template <int DT, typename FA, typename FB>
 __device__ __forceinline__ void phase_mfma(floatx4 (&acc)[8][4], const FA& af, const FB& bf, int m0, int n0) {
-  if constexpr (DT == DT_FP8U) stg_mfma_unscaled(acc, af, bf, m0, n0);
+  if constexpr (DT == DT_FP8U) stg_mfma<0>(acc, af, bf, m0, n0);
   else stg_mfma(acc, af, bf, m0, n0);
 }
 template <>
@@ -387,7 +375,8 @@ gemm_v3_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
     }
     // C through the wave's LDS patch as in the fp32 epilogue, leaving as 8 bf16 (16 bytes) per lane: one
     // store instruction covers 8 rows x 128 contiguous bytes
-    constexpr int LD = 64 + 4;
+    using W = PatchWalk<4, 8>;
+    constexpr int LD = W::LD;
     __builtin_amdgcn_s_barrier();
     float* patch = reinterpret_cast<float*>(smem) + wid * (16 * LD);
     __bf16* __restrict__ Cb = static_cast<__bf16*>(Cv);
@@ -398,8 +387,8 @@ gemm_v3_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
 #pragma unroll
         for (int j = 0; j < 4; ++j) patch[(fq * 4 + j) * LD + n * 16 + frow] = acc[m][n][j];
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int r = q * 8 + (lane >> 3), c8 = (lane & 7) * 8;
+      for (int q = 0; q < W::STEPS; ++q) {
+        const int r = W::row(lane, q), c8 = W::col(lane);
         const floatx4 lo = *reinterpret_cast<const floatx4*>(patch + r * LD + c8);
         const floatx4 hi = *reinterpret_cast<const floatx4*>(patch + r * LD + c8 + 4);
         const floatx8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -411,7 +400,8 @@ gemm_v3_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
     // Each 16x64 fp32 slice goes through the wave's own LDS patch (no DMA is in flight and every
     // fragment read retired before the last barrier), then leaves as 16-byte row pieces: one store
     // instruction covers 4 rows x 256 contiguous bytes instead of 4 rows x 64.
-    constexpr int LD = 64 + 4;
+    using W = PatchWalk<4, 4>;
+    constexpr int LD = W::LD;
     __builtin_amdgcn_s_barrier();
     float* patch = reinterpret_cast<float*>(smem) + wid * (16 * LD);
 #pragma unroll
@@ -421,8 +411,8 @@ gemm_v3_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
 #pragma unroll
         for (int j = 0; j < 4; ++j) patch[(fq * 4 + j) * LD + n * 16 + frow] = acc[m][n][j];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = q * 4 + (lane >> 4), c4 = (lane & 15) * 4;
+      for (int q = 0; q < W::STEPS; ++q) {
+        const int r = W::row(lane, q), c4 = W::col(lane);
         const floatx4 v = *reinterpret_cast<const floatx4*>(patch + r * LD + c4);
 #ifdef DIAG_GEMM_NO_STORE  // lab build (tools/gemm_stamps.py --no-store): everything but the C write itself
         if (N > (1 << 30))

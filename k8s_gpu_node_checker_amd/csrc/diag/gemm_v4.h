@@ -143,16 +143,18 @@ struct V4F8Frags {
   u32x4 alo[8], ahi[8], blo[8], bhi[8];
 };
 
+// a fragment's two 16-byte chunks as the MFMA's 32-byte operand
+__device__ __forceinline__ i32x8 v4_op8(const u32x4& lo, const u32x4& hi) {
+  return __builtin_bit_cast(i32x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
 __device__ __forceinline__ void v4_mfma8(floatx4& acc, const u32x4& alo, const u32x4& ahi, const u32x4& blo,
                                          const u32x4& bhi) {
-  const i32x8 a = __builtin_bit_cast(i32x8, __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7));
-  const i32x8 b = __builtin_bit_cast(i32x8, __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7));
+  const i32x8 a = v4_op8(alo, ahi), b = v4_op8(blo, bhi);
   asm volatile("v_mfma_f32_16x16x128_f8f6f4 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void v4_mfma8_first(floatx4& acc, const u32x4& alo, const u32x4& ahi, const u32x4& blo,
                                                const u32x4& bhi) {
-  const i32x8 a = __builtin_bit_cast(i32x8, __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7));
-  const i32x8 b = __builtin_bit_cast(i32x8, __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7));
+  const i32x8 a = v4_op8(alo, ahi), b = v4_op8(blo, bhi);
   asm volatile("v_mfma_f32_16x16x128_f8f6f4 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
 }
 template <int OFF>
@@ -432,7 +434,7 @@ gemm_v4_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
     return;
   }
   // epilogue through each wave's own LDS patch (16 rows x 128 columns of fp32), as v3's
-  constexpr int LD = 128 + 4;
+  constexpr int LD = PatchWalk<8, 4>::LD;
   float* patch = reinterpret_cast<float*>(smem) + wid * (16 * LD);
   if constexpr (OUT == OUT_BF16_CK) {
     // column sums over the wave's 128 rows in v3's order (m, then j, then the 4 lanes fq holding the column)
@@ -458,7 +460,8 @@ gemm_v4_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
       for (int n = 0; n < 8; ++n)
 #pragma unroll
         for (int j = 0; j < 4; ++j) patch[(fq * 4 + j) * LD + n * 16 + frow] = acc[m][n][j];
-      // 8 bf16 (16 bytes) per lane: one store instruction covers 4 rows x 256 contiguous bytes
+      // 8 bf16 (16 bytes) per lane: one store instruction covers 4 rows x 256 contiguous bytes.  PatchWalk<8, 8>,
+      // with its shifts and masks written out: the compiler does not know v_mbcnt's lane id to be non-negative
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int r = q * 4 + (lane >> 4), c8 = (lane & 15) * 8;
@@ -477,7 +480,7 @@ gemm_v4_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, void
       for (int n = 0; n < 8; ++n)
 #pragma unroll
         for (int j = 0; j < 4; ++j) patch[(fq * 4 + j) * LD + n * 16 + frow] = acc[m][n][j];
-      // one store instruction covers 2 rows x 512 contiguous bytes
+      // one store instruction covers 2 rows x 512 contiguous bytes (PatchWalk<8, 4> written out, as above)
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int r = q * 2 + (lane >> 5), c4 = (lane & 31) * 4;
@@ -622,7 +625,8 @@ gemm_v4_tail_kernel(const u32x4* __restrict__ A, const u32x4* __restrict__ Bt, v
     }
     __syncthreads();  // the partials are read: the scratch becomes the waves' store patches
     // bf16 C through each wave's own patch (16 rows x 64 fp32 columns): 16-byte row pieces per lane
-    constexpr int LD = 64 + 4;
+    using W = PatchWalk<4, 8>;
+    constexpr int LD = W::LD;
     float* patch = reinterpret_cast<float*>(scratch) + wid * (16 * LD);
     __bf16* __restrict__ Cb = static_cast<__bf16*>(Cv);
 #pragma unroll
@@ -633,8 +637,8 @@ gemm_v4_tail_kernel(const u32x4* __restrict__ A, const u32x4* __restrict__ Bt, v
         for (int j = 0; j < 4; ++j) patch[(fq * 4 + j) * LD + n * 16 + frow] = acc[m][n][j];
       // a wave's writes to its own patch are visible to its own later reads (one wave, in order: s_waitcnt)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int rr = h * 8 + (lane >> 3), c8 = (lane & 7) * 8;
+      for (int h = 0; h < W::STEPS; ++h) {
+        const int rr = W::row(lane, h), c8 = W::col(lane);
         const floatx4 lo = *reinterpret_cast<const floatx4*>(patch + rr * LD + c8);
         const floatx4 hi = *reinterpret_cast<const floatx4*>(patch + rr * LD + c8 + 4);
         const floatx8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
