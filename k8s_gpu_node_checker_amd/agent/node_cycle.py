@@ -20,7 +20,8 @@ from typing import Any, Dict, List, Optional
 
 
 def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: int = 8,
-        fabric: bool = True, xgmi_kernel: bool = False, atomics: bool = False, lanes: bool = False) -> Dict[str, Any]:
+        fabric: bool = True, xgmi_kernel: bool = False, atomics: bool = False, lanes: bool = False,
+        scalar: bool = False) -> Dict[str, Any]:
     """The cycle; returns the summary (never raises for a failed test: failures are in the result)."""
     from ..ops import diag
     from .agent import Agent
@@ -43,7 +44,8 @@ def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: 
     diag.run = counted  # type: ignore[assignment]
     try:
         ag = Agent("node-cycle", source="auto", diag_level=level, devices=list(devices), diag_when="always",
-                   diag_timeout=timeout_s, diag_parallel=parallel, **({"diag_atomics": True} if atomics else {}), **({"diag_lanes": True} if lanes else {}))
+                   diag_timeout=timeout_s, diag_parallel=parallel, **({"diag_atomics": True} if atomics else {}), **({"diag_lanes": True} if lanes else {}),
+                   **({"diag_scalar": True} if scalar else {}))
         rep = ag.probe_once()
     finally:
         diag.run = real_run  # type: ignore[assignment]
@@ -89,9 +91,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                     help="also run the atomics diagnostic on every device (ops/atomics.py)")
     ap.add_argument("--lanes", action="store_true",
                     help="also run the lanes diagnostic on every device (ops/lanes.py)")
+    ap.add_argument("--scalar", action="store_true",
+                    help="also run the scalar diagnostic on every device (ops/scalar.py)")
     args = ap.parse_args(argv)
     devices = [int(x) for x in args.devices.split(",") if x.strip()]
-    res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel, args.atomics, args.lanes)
+    res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel, args.atomics, args.lanes,
+              args.scalar)
     print(json.dumps(res, separators=(",", ":"), default=str), flush=True)
     return 0
 

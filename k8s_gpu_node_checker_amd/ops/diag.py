@@ -156,6 +156,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "regfile": "v8-255+a0-255",  # no rate verdict: the stamp says which registers a clean result covered
     "atomics": "8kinds-lane-per-element-r1",  # no rate verdict either (ops/atomics.py): which kinds a clean result covered
     "lanes": "39ops-chains4-r1",  # no rate verdict either (ops/lanes.py): which ops a clean result covered
+    # no rate verdict either (ops/scalar.py): the ops, SGPRs and load kinds a clean result covered
+    "scalar": "83ops-chains4+s20-31,s33-95+7loads-r1",
 }
 
 
@@ -865,6 +867,14 @@ def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return lanes.lanes_test(device, **kw)
 
 
+def scalar_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in scalar diagnostic (``ops/scalar.scalar_test``, its own library): the scalar ALU one native
+    instruction per op against the host's model, the SGPR file of every SIMD under patterns, and every width of
+    scalar load through the scalar data cache.  No level runs it; ``run(extra=("scalar",))`` does."""
+    from . import scalar  # lazily: only who asks for the test needs libmi355x_scalar.so
+    return scalar.scalar_test(device, **kw)
+
+
 def _xcd_slices(fn: str, name: str, device: int, slice_bytes: int, passes: int, blocks_per_cu: int, seed: int,
                 inject_xcd: int, inject_word: int, *more: Any) -> Tuple[float, int, List[int], Dict[str, Any], str]:
     """What :func:`l2_bandwidth` and :func:`hbm_xcd` share: the call (``more`` = further out-parameters of ``fn``) and
@@ -1168,9 +1178,10 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "valu": ("valu_burn", {}), "regfile": ("regfile_test", {}), "host_link": ("host_link", {}),
     "atomics": ("atomics_test", {}),  # in no level: run(extra=("atomics",))
     "lanes": ("lanes_test", {}),  # in no level: run(extra=("lanes",))
+    "scalar": ("scalar_test", {}),  # in no level: run(extra=("scalar",))
 }
 # error counts only: nothing to scale
-_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test"))
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test"))
 
 
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
@@ -1233,7 +1244,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``),
     each treated as the level's own are.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
@@ -1309,6 +1320,19 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
         return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
                 f"XCDs, {r.get('errors', 0)} wrong lanes; {r.get('ms', 0):.1f} ms, mean {rate:.0f} G crossings/s")
+    if test == "scalar":
+        p = r.get("parts") or {}
+        salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
+        said = []
+        if salu:
+            said.append(f"{len(salu.get('ops') or {})} ops x {salu.get('iters', '?')} steps {salu.get('errors', 0)} wrong")
+        if sgpr:
+            said.append(f"{sgpr.get('regs_per_wave', '?')} SGPRs x {(sgpr.get('waves_per_simd') or {}).get('max', 0):g} "
+                        f"waves per SIMD {sgpr.get('errors', 0)} wrong")
+        if smem:
+            said.append(f"{len(smem.get('kinds') or {})} load kinds {smem.get('errors', 0)} wrong")
+        return (f"{'; '.join(said) or 'no part'}; {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
+                f"{r.get('ms', 0):.1f} ms")
     if test == "regfile":
         return (f"{r.get('simds', '?')} SIMDs x {r.get('bytes_per_simd', 0) // 1024} KiB "
                 f"({r.get('regs_per_lane', '?')} registers), {r.get('errors', 0)} bad words")
@@ -1496,7 +1520,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1519,6 +1543,10 @@ def main(argv=None) -> int:
                     help="also run the lanes diagnostic on every device: every lane-crossing instruction of a wave "
                          "(DPP, permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane) checked bit for bit "
                          "against the host's model, wrong lanes located to their SIMD (ops/lanes.py)")
+    ap.add_argument("--scalar", action="store_true",
+                    help="also run the scalar diagnostic on every device: every scalar-ALU instruction against the "
+                         "host's model, the SGPR file of every SIMD under patterns, every width of scalar load "
+                         "through the scalar data cache (ops/scalar.py)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1532,7 +1560,8 @@ def main(argv=None) -> int:
                                                                                 "error": msg}, indent=1))
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
-    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes)) if on)
+    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar))
+                   if on)
     more = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.duration > 0:
         import sys as _sys

@@ -1,5 +1,5 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
-``libmi355x_lanes.so`` and ``libmi355x_fabric.so``.
+``libmi355x_lanes.so``, ``libmi355x_scalar.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -665,6 +665,281 @@ class FakeLanesLib:
         return -1
 
 
+def scalar_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeScalarLib` stands in for, read from csrc/scalar/scalar.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "scalar", "scalar.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(scalar_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+_M32, _M64 = 0xffffffff, (1 << 64) - 1
+
+
+def _s32(v: int) -> int:
+    return v - (1 << 32) if v & 0x80000000 else v
+
+
+def _s64(v: int) -> int:
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _bfe(s0: int, s1: int, bits: int, signed: bool) -> int:
+    off, w, full = s1 & (bits - 1), (s1 >> 16) & 0x7f, (1 << bits) - 1
+    if w == 0:
+        return 0
+    val = ((_s64(s0) if bits == 64 else _s32(s0)) if signed else s0) >> off
+    if off + w < bits:
+        val &= (1 << w) - 1
+        if signed and val >> (w - 1):
+            val -= 1 << w
+    return val & full
+
+
+def _ffs(v: int) -> int:
+    return (v & -v).bit_length() - 1 if v else _M32
+
+
+def _lead(v: int, bits: int) -> int:
+    return bits - v.bit_length() if v else _M32
+
+
+def _spread(v: int, each) -> int:
+    return sum(each(q) for q in range(16) if (v >> (4 * q)) & 0xf)
+
+
+# the ops whose destination is a register pair
+_SCALAR_WIDE = frozenset(
+    [f"s_{k}_b64" for k in ("and", "or", "xor", "andn2", "orn2", "nand", "nor", "xnor", "not", "lshl", "lshr", "bfm", "brev",
+                            "wqm", "quadmask", "cselect")]
+    + ["s_ashr_i64", "s_bfe_u64", "s_bfe_i64", "s_bitreplicate_b64_b32"])
+
+
+def scalar_model(op: str, a: int, b: int, scc: int) -> Tuple[int, int]:
+    """csrc/scalar/scalar_ref.h's scalar_apply() in Python: ``(result, scc_out)`` of instruction ``op`` on S0 = a,
+    S1 = b (64-bit; the 32-bit ops read the low halves) with SCC = ``scc`` before it."""
+    a32, b32, ai, bi = a & _M32, b & _M32, _s32(a & _M32), _s32(b & _M32)
+    ovf = lambda v: int(not -(1 << 31) <= v < (1 << 31))  # noqa: E731
+    keep, nz = "keep", "nz"
+    addk, mulk = 0x6b35, -0x2c4b
+    table = {
+        "s_add_u32": lambda: (a32 + b32, (a32 + b32) >> 32), "s_addc_u32": lambda: (a32 + b32 + scc, (a32 + b32 + scc) >> 32),
+        "s_sub_u32": lambda: (a32 - b32, int(b32 > a32)), "s_subb_u32": lambda: (a32 - b32 - scc, int(b32 + scc > a32)),
+        "s_add_i32": lambda: (ai + bi, ovf(ai + bi)), "s_sub_i32": lambda: (ai - bi, ovf(ai - bi)),
+        "s_absdiff_i32": lambda: (abs(_s32((a32 - b32) & _M32)), nz),
+        "s_lshl1_add_u32": lambda: ((a32 << 1) + b32, ((a32 << 1) + b32) >> 32 != 0),
+        "s_lshl2_add_u32": lambda: ((a32 << 2) + b32, ((a32 << 2) + b32) >> 32 != 0),
+        "s_lshl3_add_u32": lambda: ((a32 << 3) + b32, ((a32 << 3) + b32) >> 32 != 0),
+        "s_lshl4_add_u32": lambda: ((a32 << 4) + b32, ((a32 << 4) + b32) >> 32 != 0),
+        "s_addk_i32": lambda: (ai + addk, ovf(ai + addk)),
+        "s_mul_i32": lambda: (a32 * b32, keep), "s_mul_hi_u32": lambda: ((a32 * b32) >> 32, keep),
+        "s_mul_hi_i32": lambda: ((ai * bi) >> 32, keep), "s_mulk_i32": lambda: (ai * mulk, keep),
+        "s_and": lambda x, y: x & y, "s_or": lambda x, y: x | y, "s_xor": lambda x, y: x ^ y,
+        "s_andn2": lambda x, y: x & ~y, "s_orn2": lambda x, y: x | ~y, "s_nand": lambda x, y: ~(x & y),
+        "s_nor": lambda x, y: ~(x | y), "s_xnor": lambda x, y: ~(x ^ y), "s_not": lambda x, y: ~x,
+        "s_lshl_b32": lambda: (a32 << (b32 & 31), nz), "s_lshr_b32": lambda: (a32 >> (b32 & 31), nz),
+        "s_ashr_i32": lambda: (ai >> (b32 & 31), nz), "s_lshl_b64": lambda: ((a << (b32 & 63)) & _M64, nz),
+        "s_lshr_b64": lambda: (a >> (b32 & 63), nz), "s_ashr_i64": lambda: ((_s64(a) >> (b32 & 63)) & _M64, nz),
+        "s_bfm_b32": lambda: (((1 << (a32 & 31)) - 1) << (b32 & 31), keep),
+        "s_bfm_b64": lambda: ((((1 << (a32 & 63)) - 1) << (b32 & 63)) & _M64, keep),
+        "s_bfe_u32": lambda: (_bfe(a32, b32, 32, False), nz), "s_bfe_i32": lambda: (_bfe(a32, b32, 32, True), nz),
+        "s_bfe_u64": lambda: (_bfe(a, b32, 64, False), nz), "s_bfe_i64": lambda: (_bfe(a, b32, 64, True), nz),
+        "s_bcnt0_i32_b32": lambda: (32 - bin(a32).count("1"), nz), "s_bcnt1_i32_b64": lambda: (bin(a).count("1"), nz),
+        "s_ff0_i32_b32": lambda: (_ffs(~a32 & _M32), keep), "s_ff1_i32_b64": lambda: (_ffs(a), keep),
+        "s_flbit_i32_b32": lambda: (_lead(a32, 32), keep),
+        "s_flbit_i32": lambda: (_lead(~a32 & _M32 if ai < 0 else a32, 32), keep),
+        "s_flbit_i32_i64": lambda: (_lead(~a & _M64 if a >> 63 else a, 64), keep),
+        "s_brev_b32": lambda: (int(f"{a32:032b}"[::-1], 2), keep), "s_brev_b64": lambda: (int(f"{a:064b}"[::-1], 2), keep),
+        "s_bitset0_b32": lambda: (b32 & ~(1 << (a32 & 31)), keep), "s_bitset1_b32": lambda: (b32 | (1 << (a32 & 31)), keep),
+        "s_wqm_b64": lambda: (_spread(a, lambda q: 0xf << (4 * q)), nz),
+        "s_quadmask_b64": lambda: (_spread(a, lambda q: 1 << q), nz),
+        "s_bitreplicate_b64_b32": lambda: (sum(3 << (2 * i) for i in range(32) if (a32 >> i) & 1), keep),
+        "s_min_i32": lambda: (a32 if ai < bi else b32, int(ai < bi)), "s_min_u32": lambda: (min(a32, b32), int(a32 < b32)),
+        "s_max_i32": lambda: (a32 if ai > bi else b32, int(ai > bi)), "s_max_u32": lambda: (max(a32, b32), int(a32 > b32)),
+        "s_cselect_b32": lambda: (a32 if scc else b32, keep), "s_cselect_b64": lambda: ((a if scc else b), keep),
+        "s_cmov_b32": lambda: (a32 if scc else b32, keep),
+        "s_sext_i32_i8": lambda: (_s32((a32 << 24) & _M32) >> 24, keep), "s_sext_i32_i16": lambda: (_s32((a32 << 16) & _M32) >> 16, keep),
+        "s_abs_i32": lambda: (abs(ai), nz),
+        "s_pack_ll_b32_b16": lambda: ((a32 & 0xffff) | (b32 << 16), keep),
+        "s_pack_lh_b32_b16": lambda: ((a32 & 0xffff) | (b32 & 0xffff0000), keep),
+        "s_pack_hh_b32_b16": lambda: ((a32 >> 16) | (b32 & 0xffff0000), keep),
+        "s_cmp_eq_i32": lambda: (0, ai == bi), "s_cmp_lg_u32": lambda: (0, a32 != b32), "s_cmp_gt_i32": lambda: (0, ai > bi),
+        "s_cmp_ge_u32": lambda: (0, a32 >= b32), "s_cmp_lt_u32": lambda: (0, a32 < b32), "s_cmp_lt_i32": lambda: (0, ai < bi),
+        "s_cmp_le_i32": lambda: (0, ai <= bi), "s_cmp_eq_u64": lambda: (0, a == b),
+        "s_bitcmp0_b32": lambda: (0, not (a32 >> (b32 & 31)) & 1), "s_bitcmp1_b32": lambda: (0, (a32 >> (b32 & 31)) & 1),
+    }
+    if op in table:
+        r, rule = table[op]()
+    else:  # the logic ops, in both widths
+        stem = op.rpartition("_")[0]
+        r, rule = (table[stem](a, b) if op in _SCALAR_WIDE else table[stem](a32, b32)), nz
+    wide = op in _SCALAR_WIDE
+    r &= _M64 if wide else _M32
+    return r, (scc & 1 if rule == keep else int(r != 0) if rule == nz else int(bool(rule)))
+
+
+class FakeScalarLib:
+    """``libmi355x_scalar.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every part clean on every SIMD, and
+    ``scalar_apply`` answered by :func:`scalar_model`.
+
+    bad:      ``{(device, part, index): wrong words}`` with part "salu" (index: op), "sgpr" (index 0) or "smem"
+              (index: kind), all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2); the first of them is chain 1 /
+              register s41 under the inverse pattern / table word 0x69, read as ``want ^ 0x100``
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``salu{device}``, ``sgpr{device}``, ``smem{device}`` in ``calls``: empty = never called."""
+
+    OPS = 83
+    KINDS = 7
+    SLOTS = 4096
+    SGPR_LO, SGPR_HI, SGPR_REGS = 20, 95, 75
+    WANT = 0x5CA1A29E
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, str, int], int]] = None,
+                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 physical: Optional[int] = None):
+        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
+        self.physical = physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def scalar_last_error(self) -> bytes:
+        return self.err
+
+    def scalar_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def scalar_slots(self) -> int:
+        return self.SLOTS
+
+    def scalar_sgpr_lo(self) -> int:
+        return self.SGPR_LO
+
+    def scalar_sgpr_hi(self) -> int:
+        return self.SGPR_HI
+
+    def scalar_sgpr_regs(self) -> int:
+        return self.SGPR_REGS
+
+    def _device(self, device: int, part: str) -> int:
+        """The node's ordinal of ``device`` (logged), or -1 with the error set."""
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"{part}{device}")
+        return device
+
+    def _map(self, simd_map, grid: int, per_cu: int, launches: int, ticks: int) -> None:
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = ticks * launches
+
+    def _wrong(self, simd_map, wrong: int) -> None:
+        if wrong:
+            simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+            simd_map[3 * self.bad_row + 1] += wrong
+
+    def scalar_salu(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
+                    errors, first_where, got, want, ms, simd_map, blocks_run):
+        device = self._device(device, "salu")
+        if device < 0:
+            return -1
+        listed = [ops[i] for i in range(max(0, nops))]
+        if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not listed \
+                or any(not 0 <= k < self.OPS for k in listed):
+            self.err = (b"scalar salu: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a "
+                        b"list of known ops")
+            return -2
+        grid = blocks or self.xcds * 32 * 4
+        _put(blocks_run, ctypes.c_int, grid)
+        self._map(simd_map, grid, 4, (reps + 1) * len(listed), 1000 * iters)
+        for k in range(self.OPS):
+            on = k in listed
+            wrong = self.bad.get((device, "salu", k), 0) if on else 0
+            if on and k == inject_op:
+                wrong += 1
+            errors[k] = wrong
+            first_where[k] = ((self.bad_row << 32) | 1) if wrong else (1 << 64) - 1
+            want[k] = self.WANT if wrong else 0
+            got[k] = self.WANT ^ 0x100 if wrong else 0
+            ms[k] = self.ms if on else 0.0
+            self._wrong(simd_map, wrong)
+        return 0
+
+    def scalar_sgpr(self, device, blocks, reps, hold, seed, inject_block, inject_reg, errors, first_where, got, want,
+                    ms, simd_map, blocks_run):
+        device = self._device(device, "sgpr")
+        if device < 0:
+            return -1
+        if not 0 <= device < self.n or blocks < 0 or reps < 1 or not 0 <= hold <= 65536 or not -1 <= inject_reg <= 1:
+            self.err = (b"scalar sgpr: need a valid device, blocks >= 0 (0: 7 per CU), reps >= 1, hold 0..65536 and "
+                        b"inject_reg -1, 0 (lowest) or 1 (highest)")
+            return -2
+        grid = blocks or self.xcds * 32 * 7
+        _put(blocks_run, ctypes.c_int, grid)
+        self._map(simd_map, grid, 7, reps + 1, 4000 * (hold + 1))
+        wrong = self.bad.get((device, "sgpr", 0), 0) + (inject_reg >= 0)
+        reg = (self.SGPR_LO, self.SGPR_HI)[inject_reg] if inject_reg >= 0 else 41
+        _put(errors, ctypes.c_ulonglong, wrong)
+        _put(first_where, ctypes.c_ulonglong, ((self.bad_row << 32) | ((0 if inject_reg >= 0 else 1) << 8) | reg)
+             if wrong else (1 << 64) - 1)
+        _put(want, ctypes.c_ulonglong, self.WANT if wrong else 0)
+        _put(got, ctypes.c_ulonglong, self.WANT ^ (0x10 if inject_reg >= 0 else 0x100) if wrong else 0)
+        _put(ms, ctypes.c_double, self.ms)
+        self._wrong(simd_map, wrong)
+        return 0
+
+    def scalar_smem(self, device, blocks, reps, small_bytes, large_bytes, passes, loads, kind_mask, seed, inject_word,
+                    errors, first_where, got, want, ms_hit, ms_miss, simd_map, blocks_run):
+        device = self._device(device, "smem")
+        if device < 0:
+            return -1
+        sized = all(64 <= b <= 1 << 26 and b & (b - 1) == 0 for b in (small_bytes, large_bytes))
+        if not 0 <= device < self.n or blocks < 0 or reps < 1 or not sized or not 1 <= passes <= 4096 \
+                or not 1 <= loads <= 1 << 20 or not kind_mask or kind_mask >> self.KINDS or inject_word >= small_bytes // 4:
+            self.err = (b"scalar smem: need a valid device, blocks >= 0 (0: 4 per CU), reps >= 1, table sizes that are "
+                        b"powers of two from 64 B to 64 MiB, passes 1..4096, loads 1..2^20, a mask of known kinds and "
+                        b"inject_word inside the small table")
+            return -2
+        grid = blocks or self.xcds * 32 * 4
+        _put(blocks_run, ctypes.c_int, grid)
+        self._map(simd_map, grid, 4, 2 * (reps + 1) * bin(kind_mask).count("1"), 200 * (passes + loads))
+        for k in range(self.KINDS):
+            on = bool((kind_mask >> k) & 1)
+            wrong = self.bad.get((device, "smem", k), 0) if on else 0
+            if on and inject_word >= 0:
+                wrong += 4 * grid * passes  # every wave reads the word on every pass
+            errors[k] = wrong
+            first_where[k] = ((self.bad_row << 32) | (inject_word if inject_word >= 0 else 0x69)) if wrong else (1 << 64) - 1
+            want[k] = self.WANT if wrong else 0
+            got[k] = self.WANT ^ (0x10 if inject_word >= 0 else 0x100) if wrong else 0
+            ms_hit[k] = self.ms if on else 0.0
+            ms_miss[k] = 2 * self.ms if on else 0.0
+            self._wrong(simd_map, wrong)
+        return 0
+
+    def scalar_apply(self, device, op, n, a, b, scc_in, result, scc_out):
+        from ..ops.scalar import OPS
+        if not 0 <= device < self.scalar_device_count() or not 0 <= op < self.OPS or not 1 <= n <= 1 << 20 \
+                or any(scc_in[i] > 1 for i in range(n)):
+            self.err = b"scalar apply: need a valid device, an op of the table, 1..2^20 rows and scc_in 0 or 1"
+            return -2
+        for i in range(n):
+            result[i], scc_out[i] = scalar_model(OPS[op], int(a[i]), int(b[i]), int(scc_in[i]))
+        return 0
+
+
 class FakeFabricLib:
     """``libmi355x_fabric.so`` (in-process RCCL communicator over the node's GPUs)."""
 
@@ -749,10 +1024,10 @@ class NarrowedDiagLib:
 
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
-            lanes: Optional[Dict] = None, **diag_kw) -> None:
-    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics`` and ``ops.lanes`` use the fakes:
-    ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
-    ``FakeAtomicsLib(n, **atomics)`` and ``FakeLanesLib(n, **lanes)``.  The node agent's diagnostic children run it first when the agent is given
+            lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, **diag_kw) -> None:
+    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes`` and ``ops.scalar``
+    use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
+    ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
     child code path runs unchanged on CPU with scripted GPUs; a child narrowed to one GPU (``HIP_VISIBLE_DEVICES``)
     sees only that one, as under HIP."""
@@ -774,3 +1049,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import lanes as lanes_mod
     llib = FakeLanesLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(lanes or {}))
     lanes_mod.lib = lambda: llib
+    from ..ops import scalar as scalar_mod
+    slib = FakeScalarLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(scalar or {}))
+    scalar_mod.lib = lambda: slib
