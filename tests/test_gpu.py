@@ -883,17 +883,25 @@ def test_mfma_burn_rejects_inexact_iteration_counts():
         diag.mfma_burn(0, kinds=("mxfp4",), iters=4096, reps=1)
 
 
-@pytest.mark.parametrize("lds_epilogue", [False, True])
-@pytest.mark.parametrize("m,n,k", [(256, 256, 128), (256, 512, 256), (512, 256, 384), (768, 512, 512),
-                                   (1024, 768, 8192), (4096, 4096, 4096)])
-def test_mxfp8_gemm_matches_fp32_reference(dev, m, n, k, lds_epilogue):
-    """MX-fp8 (E4M3) GEMM on the staggered v3 pipeline vs torch on the same fp8 values in fp32."""
+_MXFP8_SHAPES = [(256, 256, 128), (256, 512, 256), (512, 256, 384), (768, 512, 512), (1024, 768, 8192),
+                 (4096, 4096, 4096)]
+
+
+@pytest.mark.parametrize("m,n,k,variant,lds_epilogue",
+                         [pytest.param(*s, "v3", epi, id="-".join(map(str, s + (epi,))))
+                          for epi in (False, True) for s in _MXFP8_SHAPES] +
+                         [pytest.param(*s, "auto", True, id="-".join(map(str, s + ("auto",)))) for s in _MXFP8_SHAPES])
+def test_mxfp8_gemm_matches_fp32_reference(dev, m, n, k, variant, lds_epilogue):
+    """fp8 (E4M3) GEMM vs the same fp8 values multiplied in fp64.  ``v3``: the staggered v3 pipeline on the scaled MX
+    MFMA (``fp8_unscaled=False``, unit scales) with the direct and the LDS-staged epilogue.  ``auto``: what production
+    launches, the four-wave v4 kernel on the unscaled MFMA (``fp8_variant()``), which has one epilogue."""
     from k8s_gpu_node_checker_amd.ops import diag
     g = torch.Generator(device=dev).manual_seed(m + 3 * n + 7 * k)
     a = torch.randn(m, k, device=dev, generator=g).to(torch.float8_e4m3fn)
     bt = torch.randn(n, k, device=dev, generator=g).to(torch.float8_e4m3fn)
     c = torch.full((m, n), float("nan"), device=dev, dtype=torch.float32)
-    with diag.gemm_config(epilogue=lds_epilogue):
+    cfg = dict(variant="v3", epilogue=lds_epilogue, fp8_unscaled=False) if variant == "v3" else {}
+    with diag.gemm_config(**cfg):
         diag.gemm_fp8_launch(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k,
                              torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
@@ -908,6 +916,8 @@ def test_mxfp8_gemm_matches_fp32_reference(dev, m, n, k, lds_epilogue):
 
 
 def test_mxfp8_gemm_identity_asymmetric(dev):
+    """A = I with an asymmetric B through the default fp8 kernel -- the four-wave v4 kernel on the unscaled MFMA,
+    not the MX v3 one the name recalls -- catches a transposed or permuted C write."""
     from k8s_gpu_node_checker_amd.ops import diag
     m = n = 256
     k = 256
