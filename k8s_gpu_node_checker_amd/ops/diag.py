@@ -158,6 +158,7 @@ KERNEL_REVISION: Dict[str, str] = {
     "lanes": "39ops-chains4-r1",  # no rate verdict either (ops/lanes.py): which ops a clean result covered
     # no rate verdict either (ops/scalar.py): the ops, SGPRs and load kinds a clean result covered
     "scalar": "83ops-chains4+s20-31,s33-95+7loads-r1",
+    "matrix": "34ops-steps4-exact-r1",  # no rate verdict either (ops/matrix.py): which ops a clean result covered
 }
 
 
@@ -859,6 +860,15 @@ def atomics_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return atomics.atomics_test(device, **kw)
 
 
+def matrix_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in matrix diagnostic (``ops/matrix.matrix_test``, its own library): every MFMA family of the matrix
+    cores (fp32, fp16, bf16, int8, fp64, bf8, f8f6f4 with and without block scales, sparse) on operands whose sums
+    are exact in any order, every accumulator element checked bit for bit against the host's model.  No level runs it;
+    ``run(extra=("matrix",))`` does."""
+    from . import matrix  # lazily: only who asks for the test needs libmi355x_matrix.so
+    return matrix.matrix_test(device, **kw)
+
+
 def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in lanes diagnostic (``ops/lanes.lanes_test``, its own library): every lane-crossing instruction of a
     wave (DPP, the permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane / readfirstlane) in chains that
@@ -1179,9 +1189,10 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "atomics": ("atomics_test", {}),  # in no level: run(extra=("atomics",))
     "lanes": ("lanes_test", {}),  # in no level: run(extra=("lanes",))
     "scalar": ("scalar_test", {}),  # in no level: run(extra=("scalar",))
+    "matrix": ("matrix_test", {}),  # in no level: run(extra=("matrix",))
 }
 # error counts only: nothing to scale
-_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test"))
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test"))
 
 
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
@@ -1244,7 +1255,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``),
     each treated as the level's own are.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
@@ -1320,6 +1331,10 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
         return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
                 f"XCDs, {r.get('errors', 0)} wrong lanes; {r.get('ms', 0):.1f} ms, mean {rate:.0f} G crossings/s")
+    if test == "matrix":
+        rows = r.get("ops") or {}
+        return (f"{len(rows)} ops x {r.get('iters', '?')} rounds on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+                f"XCDs, {r.get('errors', 0)} wrong elements; {r.get('ms', 0):.1f} ms")
     if test == "scalar":
         p = r.get("parts") or {}
         salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
@@ -1520,7 +1535,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1547,6 +1562,10 @@ def main(argv=None) -> int:
                     help="also run the scalar diagnostic on every device: every scalar-ALU instruction against the "
                          "host's model, the SGPR file of every SIMD under patterns, every width of scalar load "
                          "through the scalar data cache (ops/scalar.py)")
+    ap.add_argument("--matrix", action="store_true",
+                    help="also run the matrix diagnostic on every device: every MFMA family of the matrix cores "
+                         "(fp32, fp16, bf16, int8, fp64, bf8, f8f6f4, sparse) on exact operands, every "
+                         "accumulator element checked bit for bit against the host's model (ops/matrix.py)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1560,7 +1579,8 @@ def main(argv=None) -> int:
                                                                                 "error": msg}, indent=1))
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
-    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar))
+    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
+                                             ("matrix", args.matrix))
                    if on)
     more = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.duration > 0:

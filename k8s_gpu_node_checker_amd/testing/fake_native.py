@@ -1,5 +1,5 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
-``libmi355x_lanes.so``, ``libmi355x_scalar.so`` and ``libmi355x_fabric.so``.
+``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -665,6 +665,93 @@ class FakeLanesLib:
         return -1
 
 
+def matrix_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "matrix", "matrix.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(matrix_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeMatrixLib:
+    """``libmi355x_matrix.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD.
+
+    bad:      ``{(device, op index): wrong elements}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the
+              first of them lane 9, register 1, read as ``want ^ 0x100``
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``matrix{device}`` in ``calls``: empty = never called."""
+
+    OPS = 34
+    SLOTS = 4096
+    WANT = 0x4A82C64E
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
+                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.2,
+                 physical: Optional[int] = None):
+        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
+        self.physical = physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def matrix_last_error(self) -> bytes:
+        return self.err
+
+    def matrix_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def matrix_slots(self) -> int:
+        return self.SLOTS
+
+    def matrix_test(self, device, blocks, iters, reps, ops, n_ops, seed, inject_op, inject_block, inject_skip_step,
+                    errors, first_where, got, want, ms, simd_map, blocks_run):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"matrix{device}")
+        chosen = [int(ops[i]) for i in range(n_ops)]
+        if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not chosen \
+                or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
+            self.err = (b"matrix test: need a valid device, blocks >= 0 (0: 2 per CU), iters 1..2^20, reps >= 1 and a "
+                        b"list of distinct known ops")
+            return -2
+        grid = blocks or self.xcds * 32 * 2
+        _put(blocks_run, ctypes.c_int, grid)
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        launches = (reps + 1) * len(chosen)
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = 1000 * iters * launches
+        for k in range(self.OPS):
+            on = k in chosen
+            wrong = self.bad.get((device, k), 0) if on else 0
+            if on and k == inject_op:
+                wrong += 1
+            errors[k] = wrong
+            first_where[k] = ((self.bad_row << 16) | (9 << 8) | 1) if wrong else (1 << 64) - 1
+            want[k] = self.WANT if wrong else 0
+            got[k] = self.WANT ^ 0x100 if wrong else 0
+            ms[k] = self.ms if on else 0.0
+            if wrong:
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+        return 0
+
+    def matrix_apply(self, device, op, a, b, c, idx, scale_a, scale_b, d):
+        self.err = b"matrix apply: the stand-in has no wave to apply an instruction on"
+        return -1
+
+
 def scalar_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeScalarLib` stands in for, read from csrc/scalar/scalar.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1024,8 +1111,10 @@ class NarrowedDiagLib:
 
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
-            lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, **diag_kw) -> None:
-    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes`` and ``ops.scalar``
+            lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
+            **diag_kw) -> None:
+    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1052,3 +1141,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import scalar as scalar_mod
     slib = FakeScalarLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(scalar or {}))
     scalar_mod.lib = lambda: slib
+    from ..ops import matrix as matrix_mod
+    mlib = FakeMatrixLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(matrix or {}))
+    matrix_mod.lib = lambda: mlib
