@@ -1,6 +1,6 @@
 """Build every native component in-tree (``k8s_gpu_node_checker_amd/_native/``).
 
-``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics,lanes,scalar,matrix] [--force]``
+``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics,lanes,scalar,matrix,vmem] [--force]``
 
 =====================  ==================================================  ==========================
 artefact               source                                              toolchain
@@ -14,10 +14,11 @@ artefact               source                                              toolc
 ``libmi355x_lanes.so`` ``csrc/lanes/lanes.hip`` (lanes diagnostic)            hipcc --offload-arch=gfx950
 ``libmi355x_scalar.so`` ``csrc/scalar/scalar.hip`` (scalar diagnostic)        hipcc --offload-arch=gfx950
 ``libmi355x_matrix.so`` ``csrc/matrix/matrix.hip`` (matrix diagnostic)        hipcc --offload-arch=gfx950
+``libmi355x_vmem.so``  ``csrc/vmem/vmem.hip`` (vmem diagnostic)              hipcc --offload-arch=gfx950
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
-The seven HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``).
+The eight HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``).
 Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
 
 Outputs are rebuilt only when a source or header is newer or the build command changed (``--force`` to override).
@@ -54,7 +55,7 @@ def _targets() -> Dict[str, Dict[str, object]]:
            f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"]
     # every HIP library is built by the same line (fabric adds RCCL after its sources); includes are relative, no -I
     hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
-    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all seven share
+    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all eight share
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -121,6 +122,13 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "sources": [os.path.join(CSRC, "matrix", "matrix.hip")],
             "headers": [os.path.join(CSRC, "matrix", "matrix_ref.h"), hip_host],
             "out": os.path.join(OUT, "libmi355x_matrix.so"),
+            "cmd": hip_cmd,
+            "requires": hipcc,
+        },
+        "vmem": {
+            "sources": [os.path.join(CSRC, "vmem", "vmem.hip")],
+            "headers": [os.path.join(CSRC, "vmem", "vmem_ref.h"), hip_host],
+            "out": os.path.join(OUT, "libmi355x_vmem.so"),
             "cmd": hip_cmd,
             "requires": hipcc,
         },
@@ -194,7 +202,7 @@ def build(only: Optional[Sequence[str]] = None, force: bool = False, verbose: bo
 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,lanes,scalar,matrix,fabric")
+    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,lanes,scalar,matrix,vmem,fabric")
     ap.add_argument("--force", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)

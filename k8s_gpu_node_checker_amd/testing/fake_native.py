@@ -1,5 +1,6 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
-``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so`` and ``libmi355x_fabric.so``.
+``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so`` and
+``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -752,6 +753,193 @@ class FakeMatrixLib:
         return -1
 
 
+def vmem_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeVmemLib` stands in for, read from csrc/vmem/vmem.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "vmem", "vmem.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(vmem_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeVmemLib:
+    """``libmi355x_vmem.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every part clean on every SIMD.
+
+    bad:      ``{(device, op index): wrong words}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the first
+              of them lane 9, chain 1, read as ``want ^ 0x100``
+    bad_l1:   ``{device: wrong reads}`` of word 33 of slice 3, on the same row's CU
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``vmem{device}`` (once per test: by the walks) in ``calls``: empty = never called."""
+
+    OPS = 59
+    LOADS = 36
+    SLOTS = 4096
+    WANT = 0x4A82C64E
+    FORMS = (b"global_load_lds_dword", b"global_load_lds_dwordx4", b"buffer_load_dword_lds", b"buffer_load_dwordx4_lds")
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
+                 bad_l1: Optional[Dict[int, int]] = None, bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2,
+                 xcds: int = 8, ms: float = 0.2, physical: Optional[int] = None):
+        self.n, self.bad, self.bad_l1, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), dict(bad_l1 or {}), bad_row, xcds, ms
+        self.physical = physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def vmem_last_error(self) -> bytes:
+        return self.err
+
+    def vmem_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def vmem_slots(self) -> int:
+        return self.SLOTS
+
+    def vmem_ops(self) -> int:
+        return self.OPS
+
+    def vmem_loads(self) -> int:
+        return self.LOADS
+
+    def vmem_walk_reads(self, op, seed, iters, word) -> int:
+        if not 0 <= op < self.LOADS or not 1 <= iters <= 1 << 16 or not 0 <= word < 16384:
+            self.err = b"vmem walk_reads: need a load op, iters 1..2^16 and a word of the table"
+            return -2
+        return (op + word) & 1
+
+    def _device(self, device: int) -> int:
+        """The node's ordinal of ``device``, -1 (with the error set) when a narrowed process asks for another."""
+        if self.physical is None:
+            return device
+        if device != 0:
+            self.err = b"hipSetDevice(device): invalid device ordinal"
+            return -1
+        return self.physical
+
+    def _grid(self, blocks, blocks_run, simd_map, launches, ticks) -> int:
+        grid = blocks or self.xcds * 32 * 2
+        _put(blocks_run, ctypes.c_int, grid)
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = ticks * launches
+        return grid
+
+    def _blame(self, simd_map, wrong: int) -> None:
+        simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+        simd_map[3 * self.bad_row + 1] += wrong
+
+    def vmem_walks(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
+                   inject_table_word, errors, first, ms, simd_map, blocks_run):
+        device = self._device(device)
+        if device < 0:
+            return -1
+        self.calls.append(f"vmem{device}")
+        chosen = [int(ops[i]) for i in range(nops)]
+        if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1 <= iters <= 1 << 16 or reps < 1 or not chosen \
+                or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
+            self.err = (b"vmem walks: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16, reps >= 1 and a "
+                        b"list of distinct known ops")
+            return -2
+        self._grid(blocks, blocks_run, simd_map, (reps + 1) * len(chosen), 1000 * iters)
+        for k in range(self.OPS):
+            on = k in chosen
+            wrong = self.bad.get((device, k), 0) if on else 0
+            if on and k == inject_op:
+                wrong += 1
+            if on and k < self.LOADS and inject_table_word >= 0 and self.vmem_walk_reads(k, seed, iters, inject_table_word):
+                wrong += 4 * (blocks or self.xcds * 64)
+            errors[k] = wrong
+            first[4 * k] = ((self.bad_row << 32) | (9 << 8) | 1) if wrong else (1 << 64) - 1
+            first[4 * k + 1] = 0
+            first[4 * k + 2] = self.WANT ^ 0x100 if wrong else 0
+            first[4 * k + 3] = self.WANT if wrong else 0
+            ms[k] = self.ms if on else 0.0
+            if wrong:
+                self._blame(simd_map, wrong)
+        return 0
+
+    def vmem_bounds(self, device, blocks, n, seed, leak, errors, first, ms, simd_map, blocks_run):
+        device = self._device(device)
+        if device < 0:
+            return -1
+        if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1024 <= n <= 65536 or n & (n - 1):
+            self.err = (b"vmem bounds: need a valid device, blocks 0..8192 (0: 2 per CU) and n a power of two from 1 KiB "
+                        b"to 64 KiB")
+            return -2
+        grid = self._grid(blocks, blocks_run, simd_map, 16, 100 * n)
+        for k in range(8):
+            wrong = 4 * grid * (n // 32) * (4 if k & 1 else 1) if leak else 0  # the out-of-range half of every wave
+            errors[k] = wrong
+            first[4 * k] = (0 if k >= 4 else (self.bad_row << 32) | (1 << 8)) if wrong else (1 << 64) - 1
+            first[4 * k + 1] = n if wrong else 0
+            first[4 * k + 2] = self.WANT if wrong else 0
+            first[4 * k + 3] = 0
+            ms[k] = self.ms / 4
+            if wrong and k < 4:
+                self._blame(simd_map, wrong)
+        return 0
+
+    def vmem_l1(self, device, blocks, reps, slice_bytes, passes, seed, inject_block, inject_word, errors, first, ms_plain,
+                ms_sc1, simd_map, blocks_run):
+        device = self._device(device)
+        if device < 0:
+            return -1
+        if not 0 <= device < self.n or not 0 <= blocks <= 8192 or reps < 1 or not 1024 <= slice_bytes <= 1 << 20 \
+                or slice_bytes & (slice_bytes - 1) or not 1 <= passes <= 65536:
+            self.err = (b"vmem l1: need a valid device, blocks 0..8192 (0: 2 per CU), reps >= 1, slice_bytes a power of two "
+                        b"from 1 KiB to 1 MiB and passes 1..65536")
+            return -2
+        grid = self._grid(blocks, blocks_run, simd_map, 2 * reps + 1, 100 * passes)
+        if inject_block >= grid or (inject_block >= 0 and not 0 <= inject_word < slice_bytes // 4):
+            self.err = b"vmem l1: at most 8192 workgroups, inject_block inside the grid and inject_word inside the slice"
+            return -2
+        wrong = self.bad_l1.get(device, 0) + (4 * passes if inject_block >= 0 else 0)
+        _put(errors, ctypes.c_ulonglong, wrong)
+        first[0] = (self.bad_row << 32) | (3 << 8) if wrong else (1 << 64) - 1
+        first[1] = ((max(inject_block, 0) if inject_block >= 0 else 3) << 32) | (inject_word if inject_block >= 0 else 33) \
+            if wrong else 0
+        first[2] = self.WANT ^ 0x10 if wrong else 0
+        first[3] = self.WANT if wrong else 0
+        _put(ms_plain, ctypes.c_double, self.ms)
+        _put(ms_sc1, ctypes.c_double, 2 * self.ms)
+        if wrong:
+            self._blame(simd_map, wrong)
+        return 0
+
+    def vmem_ldsdma_forms(self) -> int:
+        return len(self.FORMS)
+
+    def vmem_ldsdma_name(self, form) -> bytes:
+        return self.FORMS[form] if 0 <= form < len(self.FORMS) else b""
+
+    def vmem_ldsdma(self, device, blocks, iters, reps, seed, errors, first, ms, simd_map, blocks_run):
+        device = self._device(device)
+        if device < 0:
+            return -1
+        if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1 <= iters <= 1 << 16 or reps < 1:
+            self.err = b"vmem ldsdma: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16 and reps >= 1"
+            return -2
+        self._grid(blocks, blocks_run, simd_map, (reps + 1) * len(self.FORMS), 1000 * iters)
+        for f in range(len(self.FORMS)):
+            errors[f] = 0
+            first[4 * f] = (1 << 64) - 1
+            first[4 * f + 1] = first[4 * f + 2] = first[4 * f + 3] = 0
+            ms[f] = self.ms
+        return 0
+
+    def vmem_apply(self, device, op, n, mem_words, nwords, offsets, regs, stride, num_records, out):
+        self.err = b"vmem apply: the stand-in has no wave to apply an instruction on"
+        return -1
+
+
 def scalar_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeScalarLib` stands in for, read from csrc/scalar/scalar.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1112,9 +1300,9 @@ class NarrowedDiagLib:
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
-            **diag_kw) -> None:
+            vmem: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1144,3 +1332,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import matrix as matrix_mod
     mlib = FakeMatrixLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(matrix or {}))
     matrix_mod.lib = lambda: mlib
+    from ..ops import vmem as vmem_mod
+    vlib = FakeVmemLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(vmem or {}))
+    vmem_mod.lib = lambda: vlib
