@@ -18,7 +18,8 @@ artefact               source                                              toolc
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
-The eight HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``).
+The eight HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
+lanes, scalar, matrix and vmem also share ``csrc/common/simd_report.h``.
 Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
 
 Outputs are rebuilt only when a source or header is newer or the build command changed (``--force`` to override).
@@ -56,6 +57,7 @@ def _targets() -> Dict[str, Dict[str, object]]:
     # every HIP library is built by the same line (fabric adds RCCL after its sources); includes are relative, no -I
     hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
     hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all eight share
+    simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the four SIMD-located diagnostics
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -106,28 +108,28 @@ def _targets() -> Dict[str, Dict[str, object]]:
         },
         "lanes": {
             "sources": [os.path.join(CSRC, "lanes", "lanes.hip")],
-            "headers": [os.path.join(CSRC, "lanes", "lanes_ref.h"), hip_host],
+            "headers": [os.path.join(CSRC, "lanes", "lanes_ref.h"), hip_host, simd_report],
             "out": os.path.join(OUT, "libmi355x_lanes.so"),
             "cmd": hip_cmd,
             "requires": hipcc,
         },
         "scalar": {
             "sources": [os.path.join(CSRC, "scalar", "scalar.hip")],
-            "headers": [os.path.join(CSRC, "scalar", "scalar_ref.h"), hip_host],
+            "headers": [os.path.join(CSRC, "scalar", "scalar_ref.h"), hip_host, simd_report],
             "out": os.path.join(OUT, "libmi355x_scalar.so"),
             "cmd": hip_cmd,
             "requires": hipcc,
         },
         "matrix": {
             "sources": [os.path.join(CSRC, "matrix", "matrix.hip")],
-            "headers": [os.path.join(CSRC, "matrix", "matrix_ref.h"), hip_host],
+            "headers": [os.path.join(CSRC, "matrix", "matrix_ref.h"), hip_host, simd_report],
             "out": os.path.join(OUT, "libmi355x_matrix.so"),
             "cmd": hip_cmd,
             "requires": hipcc,
         },
         "vmem": {
             "sources": [os.path.join(CSRC, "vmem", "vmem.hip")],
-            "headers": [os.path.join(CSRC, "vmem", "vmem_ref.h"), hip_host],
+            "headers": [os.path.join(CSRC, "vmem", "vmem_ref.h"), hip_host, simd_report],
             "out": os.path.join(OUT, "libmi355x_vmem.so"),
             "cmd": hip_cmd,
             "requires": hipcc,

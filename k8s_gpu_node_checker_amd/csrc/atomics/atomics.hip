@@ -307,9 +307,8 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
     ms[k] = 0.0;
     for (int x = 0; x < XCDS; ++x) xcd_waves[XCDS * k + x] = 0;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const int cus = cu_count(device);
   DevBuf buf, stats;
   const size_t array_bytes = (kind_mask & ~(1u << ATOMICS_TICKET)) ? words * 8 : 0;  // the widest kind's
@@ -366,7 +365,6 @@ int atomics_test(int device, size_t words, int adders, unsigned int kind_mask, u
     }
     ms[k] = total_ms / iters;
   }
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

@@ -1,5 +1,6 @@
 // The host-side HIP plumbing every diagnostic library shares: the error string behind *_last_error(), the checked
-// call, device allocations, timing events, polled completion, peer access and the self-check's bit flip.
+// call, the current-device scope, device allocations, timing events, polled completion, peer access, the self-check's
+// bit flip and a wave's physical location.  simd_report.h builds the SIMD-located diagnostics' report on it.
 //
 // Include it from exactly one translation unit per library.  Everything lives in an anonymous namespace, so each
 // .so keeps its own g_err (and with it its own *_last_error()) and exports none of this.
@@ -51,6 +52,25 @@ inline hipError_t event_ms(hipEvent_t a, hipEvent_t b, float* ms) {
   *ms = 0.f;
   return hipEventElapsedTime(ms, a, b);
 }
+
+// The calling thread's current device for the length of an entry point: `device` once enter() returned 0, the
+// caller's own again on every return path, a refusal or a failed HIP call included.
+struct DeviceScope {
+  int cur = -1;
+  DeviceScope() = default;
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+  int enter(int device) {
+    int c = 0;
+    HIP_CHECK(hipGetDevice(&c));
+    cur = c;
+    HIP_CHECK(hipSetDevice(device));
+    return 0;
+  }
+  ~DeviceScope() {
+    if (cur >= 0) (void)hipSetDevice(cur);
+  }
+};
 
 // Device allocation owned by its device: freed on every return path, with that device current.
 struct DevBuf {
@@ -168,6 +188,16 @@ __device__ __forceinline__ unsigned wave_slot() {
   const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_ID, all 32 bits
   const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID[3:0]
   return ((xcc & 7u) << 7) | (((hw >> 13) & 3u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
+}
+
+// ... and its SIMD inside that CU: wave_slot() << 2 | HW_ID.SIMD_ID, one of SIMD_ROWS rows of a SIMD map.  A row has
+// SIMD_MAP_COLS columns: waves run, then two counters of the map's owner (the register-file test: wrong VGPR and wrong
+// AGPR words; simd_report.h: wrong words and summed wall_clock64 ticks).
+constexpr int SIMD_ROWS = WAVE_SLOTS * 4;
+constexpr int SIMD_MAP_COLS = 3;
+__device__ __forceinline__ unsigned simd_row() {
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
+  return (wave_slot() << 2) | ((hw >> 4) & 3u);
 }
 
 }  // namespace

@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(1024) lds_test_kernel(uint32_t words, uint32_t
 constexpr int RF_VLO = 8, RF_VHI = 255, RF_ALO = 0, RF_AHI = 255;
 constexpr int RF_NV = RF_VHI - RF_VLO + 1, RF_NA = RF_AHI - RF_ALO + 1;
 constexpr int RF_REGS = RF_NV + RF_NA;  // registers of one lane holding a pattern at once
-constexpr int RF_SLOTS = BURN_SLOTS * 4;
+constexpr int RF_SLOTS = SIMD_ROWS;  // rows of its SIMD map: simd_row() of common/hip_host.h
 static_assert(RF_REGS >= 500, "the register-file test must hold at least 500 of a lane's 512 registers");
 
 // "p<t>0" .. "p<t>9": ten register names of a clobber list (a range is not accepted there)
@@ -202,8 +202,7 @@ __global__ void __launch_bounds__(256, 1) regfile_test_kernel(uint32_t seed, int
       : [key] "v"(key), [inj] "v"(inj), [which] "s"(inject_reg), [hold] "s"(hold), [vlo] "n"(RF_VLO), [vhi] "n"(RF_VHI),
         [alo] "n"(RF_ALO), [ahi] "n"(RF_AHI), [nv] "n"(RF_NV), [na] "n"(RF_NA)
       : "vcc", "scc", RF_CLOBBERS);
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
-  unsigned long long* row = simd_map + 3 * ((wave_slot() << 2) | ((hw >> 4) & 3u));
+  unsigned long long* row = simd_map + SIMD_MAP_COLS * simd_row();
   if (lane == 0) atomicAdd(row, 1ULL);
   if (bad_v) {
     atomicAdd(row + 1, static_cast<unsigned long long>(bad_v));

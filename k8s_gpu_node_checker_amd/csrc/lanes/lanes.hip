@@ -12,7 +12,9 @@
 // wave must end with come from the host's model of the op (lanes_expected() of lanes_ref.h), and every lane compares
 // bit for bit.  No LDS allocation, no scratch: lanes_test refuses to run a build that has either.
 //
-// Wrong lanes are located to their SIMD as the register-file test's are: slot = wave_slot() << 2 | HW_ID.SIMD_ID.
+// Wrong lanes are located to their SIMD as the register-file test's are: the SIMD map row is simd_row() of
+// common/hip_host.h.  The Report a launch leaves, the report() that ends the kernel and the host's Run are those of
+// common/simd_report.h.
 
 #include <hip/hip_runtime.h>
 
@@ -22,24 +24,15 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/simd_report.h"
 #include "lanes_ref.h"
 
 namespace {
 
 constexpr unsigned THREADS = 256;
-constexpr int SLOTS = WAVE_SLOTS * 4;   // rows of the SIMD map
-constexpr int MAP_COLS = 3;             // waves run, wrong lanes, summed wall_clock64 ticks
 constexpr int BLOCKS_PER_CU = 4;        // the default grid
 constexpr int MAX_ITERS = 1 << 20;
 constexpr int LANES_APPLY_BPERMUTE_Y = LANES_OPS;  // lanes_apply only: ds_bpermute with y_in as the address register
-
-// what a launch reports besides the map (device memory, zeroed by the host)
-struct Report {
-  unsigned long long errors;   // wrong lanes
-  unsigned long long claimed;  // 1 once a wrong lane has written the record below
-  unsigned long long where;    // slot << 16 | lane << 8 | chain of that lane's first wrong chain
-  unsigned long long got, want;
-};
 
 struct Pair {
   uint32_t x, y;
@@ -104,28 +97,18 @@ __global__ void __launch_bounds__(THREADS) lanes_kernel(const uint32_t* __restri
   }
   if (static_cast<int>(blockIdx.x) == flip_block && threadIdx.x == 0) x[0] ^= 0x10u;
   int bad_chain = -1;
+  uint32_t got = 0, want = 0;
 #pragma unroll
-  for (int ch = LANES_CHAINS - 1; ch >= 0; --ch)
-    if (x[ch] != expect[lane * LANES_CHAINS + ch]) bad_chain = ch;  // ends at the first wrong chain
-  const bool bad = bad_chain >= 0;
-  const unsigned long long nbad = __popcll(__ballot(bad));
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
-  const unsigned slot = (wave_slot() << 2) | ((hw >> 4) & 3u);                // < SLOTS
-  if (bad && atomicCAS(&rep->claimed, 0ULL, 1ULL) == 0ULL) {  // one lane of the launch wins and writes the record
-    rep->where = (static_cast<unsigned long long>(slot) << 16) | (lane << 8) | static_cast<unsigned>(bad_chain);
-    rep->got = x[bad_chain];
-    rep->want = expect[lane * LANES_CHAINS + bad_chain];
+  for (int ch = LANES_CHAINS - 1; ch >= 0; --ch) {  // ends at the first wrong chain
+    const uint32_t w = expect[lane * LANES_CHAINS + ch];
+    if (x[ch] != w) bad_chain = ch, got = x[ch], want = w;
   }
+  const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  if (lane == 0) {
-    unsigned long long* row = simd_map + MAP_COLS * slot;
-    atomicAdd(row, 1ULL);
-    if (nbad) {
-      atomicAdd(row + 1, nbad);
-      atomicAdd(&rep->errors, nbad);
-    }
-    atomicAdd(row + 2, dt);
-  }
+  // a wrong lane counts once; its record's `where`: SIMD map row << 16 | lane << 8 | its first wrong chain
+  const unsigned long long where =
+      (static_cast<unsigned long long>(row) << 16) | (lane << 8) | static_cast<unsigned>(bad_chain);
+  report(rep, simd_map, row, bad_chain >= 0 ? 1u : 0u, where, 0, got, want, dt);
 }
 
 // one wave, one application, returned raw: io[0..63] x, io[64..127] y, in place
@@ -181,14 +164,14 @@ const char* lanes_last_error(void) { return g_err.c_str(); }
 
 int lanes_device_count(void) { return device_count(); }
 
-int lanes_slots(void) { return SLOTS; }  // rows of lanes_test's simd_map
+int lanes_slots(void) { return SIMD_ROWS; }  // rows of lanes_test's simd_map
 
 // Every op whose bit is set in `op_mask` (bit k: LanesOp k of lanes_ref.h), one after the other, on `blocks`
 // workgroups of 4 waves (0: 4 per CU), `iters` steps of 4 chains per lane: a checked warm-up launch, then `reps`
-// timed and checked launches.  Per op k: errors[k] = wrong lanes over all its launches; first_where[k] = slot << 16 |
-// lane << 8 | chain of one wrong lane of the first launch that had any (~0: none), got[k] / want[k] that chain's
-// word and the model's; ms[k] the mean time of a timed launch.  simd_map: lanes_slots() x 3 (waves run, wrong lanes,
-// summed wall_clock64 ticks) per physical SIMD (wave_slot() << 2 | SIMD_ID), added up over every launch of every op.
+// timed and checked launches.  Per op k: errors[k] = wrong lanes over all its launches; first_where[k] = SIMD map
+// row << 16 | lane << 8 | chain of one wrong lane of the first launch that had any (~0: none), got[k] / want[k] that
+// chain's word and the model's; ms[k] the mean time of a timed launch.  simd_map: lanes_slots() x 3 (waves run, wrong lanes,
+// summed wall_clock64 ticks) per physical SIMD (simd_row()), added up over every launch of every op.
 //
 // Refused with -2 and a message: a bad device, blocks < 0, iters outside 1..2^20, reps < 1, an empty mask or unknown
 // op, a hook outside the mask or the grid; with -3: a kernel built with a scratch segment or an LDS allocation (it
@@ -210,9 +193,8 @@ int lanes_test(int device, int blocks, int iters, int reps, unsigned long long o
     g_err = "lanes test: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a mask of known ops";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
   *blocks_run = static_cast<int>(grid);
   if (inject_op >= 0 && (inject_op >= LANES_OPS || !((op_mask >> inject_op) & 1ULL) || inject_block < 0 ||
@@ -225,52 +207,35 @@ int lanes_test(int device, int blocks, int iters, int reps, unsigned long long o
     first_where[k] = ~0ULL;
     ms[k] = 0.0;
   }
-  DevBuf dexp, drep, dmap;
+  Run run;
+  if (const int rc = run.open(device)) return rc;
+  DevBuf dexp;
   HIP_CHECK(dexp.alloc(device, LANES_WAVE * LANES_CHAINS * sizeof(uint32_t)));
-  HIP_CHECK(drep.alloc(device, sizeof(Report)));
-  HIP_CHECK(dmap.alloc(device, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(dmap.ptr, 0, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-  Timer tm;
-  HIP_CHECK(tm.create());
   std::vector<uint32_t> expect(LANES_WAVE * LANES_CHAINS);
   for (int k = 0; k < LANES_OPS; ++k) {
     if (!((op_mask >> k) & 1ULL)) continue;
     hipFuncAttributes attr;
     HIP_CHECK(AllOps::attributes[k](&attr));
-    if (attr.localSizeBytes != 0 || attr.sharedSizeBytes != 0) {
-      g_err = std::string("lanes test: the kernel of ") + LANES_OP_TABLE[k].name + " was built with " +
-              std::to_string(attr.localSizeBytes) + " bytes of scratch per lane and " +
-              std::to_string(attr.sharedSizeBytes) + " bytes of LDS: it would test memory, not the crossing";
-      return -3;
-    }
+    if (const int rc = refuse_memory("lanes test", LANES_OP_TABLE[k].name, attr, ": it would test memory, not the crossing"))
+      return rc;
     lanes_expected(k, seed, iters, -1, expect.data());
     HIP_CHECK(hipMemcpy(dexp.ptr, expect.data(), expect.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     double total_ms = 0.0;
+    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
     for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
       const bool hooked = r == 0 && k == inject_op;
       const Launch l = {static_cast<const uint32_t*>(dexp.ptr), lanes_op_seed(seed, k), iters,
                         hooked && inject_skip_iter < 0 ? inject_block : -1,
                         hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
-                        static_cast<Report*>(drep.ptr), static_cast<unsigned long long*>(dmap.ptr), grid};
-      HIP_CHECK(hipMemset(drep.ptr, 0, sizeof(Report)));
+                        run.rep(), run.map(), grid};
       float t = 0.f;
-      const auto enqueue = [&] {
-        AllOps::launch[k](l);
-        return 0;
-      };
-      if (const int rc = tm.timed(enqueue, &t)) return rc;
+      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
       if (r > 0) total_ms += t;
-      Report h;
-      HIP_CHECK(hipMemcpy(&h, drep.ptr, sizeof h, hipMemcpyDeviceToHost));
-      errors[k] += h.errors;
-      if (h.claimed && first_where[k] == ~0ULL) first_where[k] = h.where, got[k] = h.got, want[k] = h.want;
     }
+    first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
     ms[k] = total_ms / reps;
   }
-  HIP_CHECK(hipMemcpy(simd_map, dmap.ptr, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipSetDevice(cur));
-  return 0;
+  return run.read_map(simd_map);
 }
 
 // One application of op `op` at step `iter` by one wave of `device`, returned raw: x_out / y_out = the two registers
@@ -283,9 +248,8 @@ int lanes_apply(int device, int op, unsigned int iter, const uint32_t* x_in, con
     g_err = "lanes apply: need a valid device and an op of the table (or one past it: ds_bpermute by y_in)";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   DevBuf io;
   HIP_CHECK(io.alloc(device, 2 * LANES_WAVE * sizeof(uint32_t)));
   uint32_t* p = static_cast<uint32_t*>(io.ptr);
@@ -296,7 +260,6 @@ int lanes_apply(int device, int op, unsigned int iter, const uint32_t* x_in, con
   HIP_CHECK(hipDeviceSynchronize());
   HIP_CHECK(hipMemcpy(x_out, p, LANES_WAVE * sizeof(uint32_t), hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(y_out, p + LANES_WAVE, LANES_WAVE * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

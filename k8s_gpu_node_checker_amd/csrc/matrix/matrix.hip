@@ -15,7 +15,9 @@
 // header's exactness rule, so the result has one value whatever the order the hardware adds in.  No LDS, no scratch:
 // matrix_test refuses to run a build that has either.
 //
-// Wrong elements are located to their SIMD as the register-file test's are: slot = wave_slot() << 2 | HW_ID.SIMD_ID.
+// Wrong elements are located to their SIMD as the register-file test's are: the SIMD map row is simd_row() of
+// common/hip_host.h.  The Report a launch leaves, the report() that ends the kernel and the host's Run are those of
+// common/simd_report.h.
 
 #include <hip/hip_runtime.h>
 
@@ -25,13 +27,12 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/simd_report.h"
 #include "matrix_ref.h"
 
 namespace {
 
 constexpr unsigned THREADS = 256;
-constexpr int SLOTS = WAVE_SLOTS * 4;   // rows of the SIMD map
-constexpr int MAP_COLS = 3;             // waves run, wrong elements, summed wall_clock64 ticks
 constexpr int BLOCKS_PER_CU = 2;        // the default grid
 constexpr int MAX_ITERS = 1 << 20;
 
@@ -49,14 +50,6 @@ typedef short shortx4 __attribute__((ext_vector_type(4)));
 typedef short shortx8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
-
-// what a launch reports besides the map (device memory, zeroed by the host)
-struct Report {
-  unsigned long long errors;   // wrong elements
-  unsigned long long claimed;  // 1 once a wrong lane has written the record below
-  unsigned long long where;    // slot << 16 | lane << 8 | register element of that lane's first wrong element
-  unsigned long long got, want;
-};
 
 // the accumulator type of op OP
 template <int OP>
@@ -249,27 +242,12 @@ __global__ void __launch_bounds__(THREADS) matrix_kernel(const MatrixOperands* _
       }
     }
   }
-  const bool bad = nbad != 0;
-  unsigned long long wave_bad = nbad;
-#pragma unroll
-  for (int off = 32; off; off >>= 1) wave_bad += __shfl_xor(wave_bad, off);
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
-  const unsigned slot = (wave_slot() << 2) | ((hw >> 4) & 3u);                // < SLOTS
-  if (bad && atomicCAS(&rep->claimed, 0ULL, 1ULL) == 0ULL) {  // one lane of the launch wins and writes the record
-    rep->where = (static_cast<unsigned long long>(slot) << 16) | (lane << 8) | static_cast<unsigned>(first);
-    rep->got = first_got;
-    rep->want = first_want;
-  }
+  const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  if (lane == 0) {
-    unsigned long long* row = simd_map + MAP_COLS * slot;
-    atomicAdd(row, 1ULL);
-    if (wave_bad) {
-      atomicAdd(row + 1, wave_bad);
-      atomicAdd(&rep->errors, wave_bad);
-    }
-    atomicAdd(row + 2, dt);
-  }
+  // a record's `where`: SIMD map row << 16 | lane << 8 | register element of the lane's first wrong element
+  const unsigned long long where =
+      (static_cast<unsigned long long>(row) << 16) | (lane << 8) | static_cast<unsigned>(first);
+  report(rep, simd_map, row, nbad, where, 0, first_got, first_want, dt);
 }
 
 // what matrix_apply hands one wave: raw registers in, raw D out
@@ -340,15 +318,15 @@ const char* matrix_last_error(void) { return g_err.c_str(); }
 
 int matrix_device_count(void) { return device_count(); }
 
-int matrix_slots(void) { return SLOTS; }  // rows of matrix_test's simd_map
+int matrix_slots(void) { return SIMD_ROWS; }  // rows of matrix_test's simd_map
 
 // Every op of `ops` (n_ops indices into MATRIX_OP_TABLE), one after the other, on `blocks` workgroups of 4 waves (0: 2
 // per CU), `iters` rounds of MATRIX_STEPS dependent instructions: a checked warm-up launch, then `reps` timed and
 // checked launches.  The result arrays hold MATRIX_OPS entries, indexed by op.  Per op k: errors[k] = wrong elements
-// over all its launches; first_where[k] = slot << 16 | lane << 8 | register element of one wrong element of the first
+// over all its launches; first_where[k] = row << 16 | lane << 8 | register element of one wrong element of the first
 // launch that had any (~0: none), got[k] / want[k] that element's bits and the model's; ms[k] the mean time of a timed
 // launch.  simd_map: matrix_slots() x 3 (waves run, wrong elements, summed wall_clock64 ticks) per physical SIMD
-// (wave_slot() << 2 | SIMD_ID), added up over every launch of every op.
+// (simd_row()), added up over every launch of every op.
 //
 // Refused with -2 and a message: a bad device, blocks < 0, iters outside 1..2^20, reps < 1, no op, an unknown or
 // repeated op, a hook outside the ops or the grid, operands the model refuses; with -3: a kernel built with a scratch
@@ -376,9 +354,8 @@ int matrix_test(int device, int blocks, int iters, int reps, const int* ops, int
             "distinct known ops";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
   *blocks_run = static_cast<int>(grid);
   if (inject_op >= 0 && (inject_op >= MATRIX_OPS || !chosen[inject_op] || inject_block < 0 ||
@@ -391,24 +368,18 @@ int matrix_test(int device, int blocks, int iters, int reps, const int* ops, int
     first_where[k] = ~0ULL;
     ms[k] = 0.0;
   }
-  DevBuf din, drep, dmap;
+  Run run;
+  if (const int rc = run.open(device)) return rc;
+  DevBuf din;
   HIP_CHECK(din.alloc(device, sizeof(MatrixOperands)));
-  HIP_CHECK(drep.alloc(device, sizeof(Report)));
-  HIP_CHECK(dmap.alloc(device, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(dmap.ptr, 0, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-  Timer tm;
-  HIP_CHECK(tm.create());
   std::vector<MatrixOperands> host(1);
   for (int i = 0; i < n_ops; ++i) {
     const int k = ops[i];
     hipFuncAttributes attr;
     HIP_CHECK(AllOps::attributes[k](&attr));
-    if (attr.localSizeBytes != 0 || attr.sharedSizeBytes != 0) {
-      g_err = std::string("matrix test: the kernel of ") + MATRIX_OP_TABLE[k].name + " was built with " +
-              std::to_string(attr.localSizeBytes) + " bytes of scratch per lane and " +
-              std::to_string(attr.sharedSizeBytes) + " bytes of LDS: it would test memory, not the matrix core";
-      return -3;
-    }
+    if (const int rc = refuse_memory("matrix test", MATRIX_OP_TABLE[k].name, attr,
+                                     ": it would test memory, not the matrix core"))
+      return rc;
     if (const int rc = matrix_expect(k, seed, 0, -1, host.data()); rc < 0) {
       g_err = std::string("matrix test: the model refuses the operands of ") + MATRIX_OP_TABLE[k].name + " (" +
               std::to_string(rc) + ")";
@@ -416,31 +387,21 @@ int matrix_test(int device, int blocks, int iters, int reps, const int* ops, int
     }
     HIP_CHECK(hipMemcpy(din.ptr, host.data(), sizeof(MatrixOperands), hipMemcpyHostToDevice));
     double total_ms = 0.0;
+    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
     for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
       const bool hooked = r == 0 && k == inject_op;
       const Launch l = {static_cast<const MatrixOperands*>(din.ptr), iters,
                         hooked && inject_skip_step < 0 ? inject_block : -1,
                         hooked && inject_skip_step >= 0 ? inject_block : -1, hooked ? inject_skip_step : -1,
-                        static_cast<Report*>(drep.ptr), static_cast<unsigned long long*>(dmap.ptr), grid};
-      HIP_CHECK(hipMemset(drep.ptr, 0, sizeof(Report)));
+                        run.rep(), run.map(), grid};
       float t = 0.f;
-      const auto enqueue = [&] {
-        AllOps::launch[k](l);
-        return 0;
-      };
-      if (const int rc = tm.timed(enqueue, &t)) return rc;
+      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
       if (r > 0) total_ms += t;
-      Report h;
-      HIP_CHECK(hipMemcpy(&h, drep.ptr, sizeof h, hipMemcpyDeviceToHost));
-      errors[k] += h.errors;
-      if (h.claimed && first_where[k] == ~0ULL) first_where[k] = h.where, got[k] = h.got, want[k] = h.want;
     }
+    first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
     ms[k] = total_ms / reps;
   }
-  HIP_CHECK(hipMemcpy(simd_map, dmap.ptr, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipSetDevice(cur));
-  return 0;
+  return run.read_map(simd_map);
 }
 
 // One application of op `op` by one wave of `device`, on raw per-lane registers: a and b hold MATRIX_AW (8) words per
@@ -453,9 +414,8 @@ int matrix_apply(int device, int op, const uint32_t* a, const uint32_t* b, const
     g_err = "matrix apply: need a valid device and an op of the table";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   std::vector<ApplyIo> host(1);
   ApplyIo& h = host[0];
   __builtin_memcpy(h.A, a, sizeof h.A);
@@ -473,7 +433,6 @@ int matrix_apply(int device, int op, const uint32_t* a, const uint32_t* b, const
   HIP_CHECK(hipDeviceSynchronize());
   HIP_CHECK(hipMemcpy(&h, io.ptr, sizeof h, hipMemcpyDeviceToHost));
   __builtin_memcpy(d, h.D, sizeof h.D);
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

@@ -15,7 +15,9 @@
 // atomics.  No LDS allocation, no scratch: every entry point refuses to run a build that has either.  ops/scalar.py
 // is its Python side; ops/diag.run(extra=("scalar",)) runs it next to a level's own tests.
 //
-// Wrong words are located to their SIMD as the register-file test's are: slot = wave_slot() << 2 | HW_ID.SIMD_ID.
+// Wrong words are located to their SIMD as the register-file test's are: the SIMD map row is simd_row() of
+// common/hip_host.h; `slot` below is that row.  The Report a launch leaves, the report() that ends the kernel and the
+// host's Run are those of common/simd_report.h.
 // The SGPR file is per SIMD; the scalar ALU and the scalar cache are shared, so their faults show on every SIMD of
 // a CU (the cache: of its neighbours too).
 
@@ -27,50 +29,22 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/simd_report.h"
 #include "scalar_ref.h"
 
 namespace {
 
 constexpr unsigned THREADS = 256;
-constexpr int SLOTS = WAVE_SLOTS * 4;   // rows of a SIMD map
-constexpr int MAP_COLS = 3;             // waves run, wrong words, summed wall_clock64 ticks
 constexpr int SALU_BLOCKS_PER_CU = 4;   // the default grids
 constexpr int SGPR_BLOCKS_PER_CU = 7;   // 4 waves each: 7 waves per SIMD, what 112 allocated SGPRs admit
 constexpr int SMEM_BLOCKS_PER_CU = 4;
 constexpr int MAX_ITERS = 1 << 20;
 constexpr uint32_t MAX_TABLE_WORDS = 1u << 24;  // 64 MiB
 
-// what a launch reports besides the map (device memory, zeroed by the host)
-struct Report {
-  unsigned long long errors;   // wrong words
-  unsigned long long claimed;  // 1 once a wave has written the record below
-  unsigned long long where;    // slot << 32 | the part's own index (chain; pattern << 8 | register; table word)
-  unsigned long long got, want;
-};
-
-__device__ __forceinline__ unsigned simd_slot() {
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
-  return (wave_slot() << 2) | ((hw >> 4) & 3u);                              // < SLOTS
-}
-
-// The end of every kernel, on lane 0: one wave of the launch writes the record of its first wrong word, every wave
-// adds itself to its SIMD's row.  Vector stores and vector atomics only.
-__device__ __forceinline__ void report(Report* rep, unsigned long long* simd_map, unsigned slot, unsigned long long nbad,
-                                       unsigned long long index, unsigned long long got, unsigned long long want,
-                                       unsigned long long dt) {
-  if ((threadIdx.x & 63u) != 0) return;
-  if (nbad && atomicCAS(&rep->claimed, 0ULL, 1ULL) == 0ULL) {
-    rep->where = (static_cast<unsigned long long>(slot) << 32) | index;
-    rep->got = got;
-    rep->want = want;
-  }
-  unsigned long long* row = simd_map + MAP_COLS * slot;
-  atomicAdd(row, 1ULL);
-  if (nbad) {
-    atomicAdd(row + 1, nbad);
-    atomicAdd(&rep->errors, nbad);
-  }
-  atomicAdd(row + 2, dt);
+// Every count here is one wave's, so lane 0 alone calls report().  A record's `where`: SIMD map row << 32 | the part's
+// own index (chain; pattern << 8 | register; table word).
+__device__ __forceinline__ unsigned long long where_of(unsigned row, unsigned index) {
+  return (static_cast<unsigned long long>(row) << 32) | index;
 }
 
 // --- salu ------------------------------------------------------------------------------------------------------
@@ -159,10 +133,11 @@ __global__ void __launch_bounds__(THREADS) salu_kernel(const uint32_t* expect, u
   const uint32_t got = ch == 0 ? x[0] : ch == 1 ? x[1] : ch == 2 ? x[2] : x[3];
   const unsigned long long wrong = __ballot(lane < SCALAR_CHAINS && got != want);
   const unsigned first = wrong ? static_cast<unsigned>(__ffsll(static_cast<long long>(wrong)) - 1) : 0u;
-  const unsigned slot = simd_slot();
+  const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, slot, __popcll(wrong), first, __builtin_amdgcn_readlane(got, static_cast<int>(first)),
-         __builtin_amdgcn_readlane(want, static_cast<int>(first)), dt);
+  const uint32_t first_got = __builtin_amdgcn_readlane(got, static_cast<int>(first));
+  const uint32_t first_want = __builtin_amdgcn_readlane(want, static_cast<int>(first));
+  if (lane == 0) report(rep, simd_map, row, __popcll(wrong), where_of(row, first), 0, first_got, first_want, dt);
 }
 
 // one wave, `n` applications one after the other, returned raw: in[3 i ..] = a, b, scc_in -> out[2 i ..] = result,
@@ -278,9 +253,9 @@ __global__ void __launch_bounds__(THREADS) sgpr_kernel(uint64_t seed, int hold, 
       : [key] "s"(key), [hold] "s"(hold), [injlo] "s"(injlo), [injhi] "s"(injhi), [lo] "n"(SG_LO), [hi] "n"(SG_HI),
         [n] "n"(SG_SPAN), [skip] "n"(SG_SKIP), [t0] "s"(t0)  // t0: the clock is read before the statement
       : "scc", SG_CLOBBERS);
-  const unsigned slot = simd_slot();
+  const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, slot, cnt, first, got, want, dt);
+  if ((threadIdx.x & 63u) == 0) report(rep, simd_map, row, cnt, where_of(row, first), 0, got, want, dt);
 }
 
 // --- smem ------------------------------------------------------------------------------------------------------
@@ -347,9 +322,9 @@ __global__ void __launch_bounds__(THREADS) smem_kernel(const uint32_t* table, ui
       }
     }
   }
-  const unsigned slot = simd_slot();
+  const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, slot, nbad, first, got, want, dt);
+  if ((threadIdx.x & 63u) == 0) report(rep, simd_map, row, nbad, where_of(row, first), 0, got, want, dt);
 }
 
 struct SmemLaunch {
@@ -379,50 +354,10 @@ Kinds<I...> kinds_of(std::integer_sequence<int, I...>);
 using AllKinds = decltype(kinds_of(std::make_integer_sequence<int, SCALAR_SMEM_KINDS>()));
 
 // --- host ------------------------------------------------------------------------------------------------------
-// -3 with a message when a kernel was built with scratch or LDS: it would test memory, not the scalar unit
-int refuse_memory(const hipFuncAttributes& attr, const std::string& what) {
-  if (attr.localSizeBytes == 0 && attr.sharedSizeBytes == 0) return 0;
-  g_err = "scalar test: the kernel of " + what + " was built with " + std::to_string(attr.localSizeBytes) +
-          " bytes of scratch per lane and " + std::to_string(attr.sharedSizeBytes) +
-          " bytes of LDS: it would test memory, not the scalar unit";
-  return -3;
+// -3 with a message when a kernel was built with scratch or LDS
+int refuse(const hipFuncAttributes& attr, const std::string& what) {
+  return refuse_memory("scalar test", what, attr, ": it would test memory, not the scalar unit");
 }
-
-// the device buffers every part needs, and one checked, timed launch
-struct Run {
-  DevBuf drep, dmap;
-  Timer tm;
-  int open(int device) {
-    HIP_CHECK(drep.alloc(device, sizeof(Report)));
-    HIP_CHECK(dmap.alloc(device, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-    HIP_CHECK(hipMemset(dmap.ptr, 0, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-    HIP_CHECK(tm.create());
-    return 0;
-  }
-  Report* rep() const { return static_cast<Report*>(drep.ptr); }
-  unsigned long long* map() const { return static_cast<unsigned long long*>(dmap.ptr); }
-  // launches through `enqueue`, adds the launch's wrong words to *errors and keeps the first record seen
-  template <typename F>
-  int launch(F&& enqueue, float* ms, unsigned long long* errors, unsigned long long* first_where, unsigned long long* got,
-             unsigned long long* want) {
-    HIP_CHECK(hipMemset(drep.ptr, 0, sizeof(Report)));
-    const auto go = [&] {
-      enqueue();
-      return 0;
-    };
-    if (const int rc = tm.timed(go, ms)) return rc;
-    Report h;
-    HIP_CHECK(hipMemcpy(&h, drep.ptr, sizeof h, hipMemcpyDeviceToHost));
-    *errors += h.errors;
-    if (h.claimed && *first_where == ~0ULL) *first_where = h.where, *got = h.got, *want = h.want;
-    return 0;
-  }
-  int read_map(unsigned long long* simd_map) {
-    HIP_CHECK(hipMemcpy(simd_map, dmap.ptr, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
 
 }  // namespace
 
@@ -432,7 +367,7 @@ const char* scalar_last_error(void) { return g_err.c_str(); }
 
 int scalar_device_count(void) { return device_count(); }
 
-int scalar_slots(void) { return SLOTS; }  // rows of every simd_map below
+int scalar_slots(void) { return SIMD_ROWS; }  // rows of every simd_map below
 
 int scalar_sgpr_lo(void) { return SG_LO; }  // the SGPR file test covers s[lo]..s[hi] of every wave
 
@@ -445,8 +380,8 @@ int scalar_sgpr_regs(void) { return SG_REGS; }  // how many of them: the reserve
 // timed and checked launches.  Per op k (arrays of the table's length): errors[k] = wrong wave-words over all its
 // launches; first_where[k] = slot << 32 | chain of one wrong word of the first launch that had any (~0: none),
 // got[k] / want[k] that chain's word and the model's; ms[k] the mean time of a timed launch.  simd_map:
-// scalar_slots() x 3 (waves run, wrong words, summed wall_clock64 ticks) per physical SIMD (wave_slot() << 2 |
-// SIMD_ID), added up over every launch of every op.
+// scalar_slots() x 3 (waves run, wrong words, summed wall_clock64 ticks) per physical SIMD (simd_row()),
+// added up over every launch of every op.
 //
 // Refused with -2 and a message: a bad device, blocks < 0, iters outside 1..2^20, reps < 1, no op or an unknown
 // one, a hook outside the list or the grid; with -3: a kernel built with a scratch segment or an LDS allocation.
@@ -470,9 +405,8 @@ int scalar_salu(int device, int blocks, int iters, int reps, const int* ops, int
     g_err = "scalar salu: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a list of known ops";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SALU_BLOCKS_PER_CU;
   *blocks_run = static_cast<int>(grid);
   if (!hook_listed || (inject_op >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid ||
@@ -494,10 +428,11 @@ int scalar_salu(int device, int blocks, int iters, int reps, const int* ops, int
     const int k = ops[i];
     hipFuncAttributes attr;
     HIP_CHECK(AllOps::attributes[k](&attr));
-    if (const int rc = refuse_memory(attr, SCALAR_OP_TABLE[k].name)) return rc;
+    if (const int rc = refuse(attr, SCALAR_OP_TABLE[k].name)) return rc;
     scalar_expected(k, seed, iters, -1, expect);
     HIP_CHECK(hipMemcpy(dexp.ptr, expect, sizeof expect, hipMemcpyHostToDevice));
     double total_ms = 0.0;
+    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
     for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
       const bool hooked = r == 0 && k == inject_op;
       const SaluLaunch l = {static_cast<const uint32_t*>(dexp.ptr), scalar_op_seed(seed, k), iters,
@@ -505,14 +440,13 @@ int scalar_salu(int device, int blocks, int iters, int reps, const int* ops, int
                             hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
                             run.rep(), run.map(), grid};
       float t = 0.f;
-      if (const int rc = run.launch([&] { AllOps::launch[k](l); }, &t, errors + k, first_where + k, got + k, want + k))
-        return rc;
+      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
       if (r > 0) total_ms += t;
     }
+    first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
     ms[k] = total_ms / reps;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -533,9 +467,8 @@ int scalar_sgpr(int device, int blocks, int reps, int hold, uint64_t seed, int i
     g_err = "scalar sgpr: need a valid device, blocks >= 0 (0: 7 per CU), reps >= 1, hold 0..65536 and inject_reg -1, 0 (lowest) or 1 (highest)";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SGPR_BLOCKS_PER_CU;
   *blocks_run = static_cast<int>(grid);
   if (inject_reg >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid)) {
@@ -547,22 +480,23 @@ int scalar_sgpr(int device, int blocks, int reps, int hold, uint64_t seed, int i
   *ms = 0.0;
   hipFuncAttributes attr;
   HIP_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(sgpr_kernel)));
-  if (const int rc = refuse_memory(attr, "the SGPR file")) return rc;
+  if (const int rc = refuse(attr, "the SGPR file")) return rc;
   Run run;
   if (const int rc = run.open(device)) return rc;
   double total_ms = 0.0;
+  unsigned long long rec[4] = {~0ULL, 0, 0, 0};
   for (int r = 0; r <= reps; ++r) {
     float t = 0.f;
     const auto enqueue = [&] {
       hipLaunchKernelGGL(sgpr_kernel, dim3(grid), dim3(THREADS), 0, nullptr, seed + static_cast<uint64_t>(r), hold,
                          r == 0 ? inject_block : -1, r == 0 ? inject_reg : -1, run.rep(), run.map());
     };
-    if (const int rc = run.launch(enqueue, &t, errors, first_where, got, want)) return rc;
+    if (const int rc = run.checked(enqueue, &t, errors, rec)) return rc;
     if (r > 0) total_ms += t;
   }
+  *first_where = rec[0], *got = rec[2], *want = rec[3];
   *ms = total_ms / reps;
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -589,9 +523,8 @@ int scalar_smem(int device, int blocks, int reps, unsigned int small_bytes, unsi
             "from 64 B to 64 MiB, passes 1..4096, loads 1..2^20, a mask of known kinds and inject_word inside the small table";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SMEM_BLOCKS_PER_CU;
   *blocks_run = static_cast<int>(grid);
   for (int k = 0; k < SCALAR_SMEM_KINDS; ++k) {
@@ -616,23 +549,23 @@ int scalar_smem(int device, int blocks, int reps, unsigned int small_bytes, unsi
     if (!((kind_mask >> k) & 1u)) continue;
     hipFuncAttributes attr;
     HIP_CHECK(AllKinds::attributes[k](&attr));
-    if (const int rc = refuse_memory(attr, SCALAR_SMEM_TABLE[k].name)) return rc;
+    if (const int rc = refuse(attr, SCALAR_SMEM_TABLE[k].name)) return rc;
     const uint32_t width = static_cast<uint32_t>(SCALAR_SMEM_TABLE[k].words);
+    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
     for (int t = 0; t < 2; ++t) {
       const uint32_t nloads = t == 0 ? static_cast<uint32_t>(passes) * (words[0] / width) : static_cast<uint32_t>(loads);
       const SmemLaunch l = {static_cast<const uint32_t*>(table[t].ptr), words[t], seed32, nloads, t, run.rep(), run.map(), grid};
       double total_ms = 0.0;
       for (int r = 0; r <= reps; ++r) {
         float ms = 0.f;
-        if (const int rc = run.launch([&] { AllKinds::launch[k](l); }, &ms, errors + k, first_where + k, got + k, want + k))
-          return rc;
+        if (const int rc = run.checked([&] { AllKinds::launch[k](l); }, &ms, errors + k, rec)) return rc;
         if (r > 0) total_ms += ms;
       }
       (t == 0 ? ms_hit : ms_miss)[k] = total_ms / reps;
     }
+    first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
   }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -648,9 +581,8 @@ int scalar_apply(int device, int op, int n, const uint64_t* a, const uint64_t* b
     g_err = "scalar apply: need a valid device, an op of the table, 1..2^20 rows and scc_in 0 or 1";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   std::vector<uint64_t> in(3 * static_cast<size_t>(n)), out(2 * static_cast<size_t>(n));
   for (int i = 0; i < n; ++i) in[3 * i] = a[i], in[3 * i + 1] = b[i], in[3 * i + 2] = scc_in[i];
   DevBuf din, dout;
@@ -662,7 +594,6 @@ int scalar_apply(int device, int op, int n, const uint64_t* a, const uint64_t* b
   HIP_CHECK(hipDeviceSynchronize());
   HIP_CHECK(hipMemcpy(out.data(), dout.ptr, out.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
   for (int i = 0; i < n; ++i) result[i] = out[2 * i], scc_out[i] = static_cast<unsigned int>(out[2 * i + 1]);
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

@@ -21,7 +21,8 @@
 //           read was served by the L1: the test reads data that should be held there, and reports both times.
 //           ldsdma: the LDS-DMA forms (global_load_lds_dword / x4, buffer_load_dword / x4 ... lds), read back from
 //           the LDS by other lanes.
-// Results leave the waves through vector stores and vector atomics only.  Only the LDS-DMA kernel has an LDS
+// Results leave the waves through vector stores and vector atomics only: the Report, report() and the host's Run of
+// common/simd_report.h, on the SIMD map rows of simd_row() (common/hip_host.h).  Only the LDS-DMA kernel has an LDS
 // allocation, no kernel has scratch: every entry point refuses a build that differs (-3).  ops/vmem.py is its Python
 // side; ops/diag.run(extra=("vmem",)) runs it next to a level's own tests.
 //
@@ -37,13 +38,12 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/simd_report.h"
 #include "vmem_ref.h"
 
 namespace {
 
 constexpr unsigned THREADS = 256;
-constexpr int SLOTS = WAVE_SLOTS * 4;  // rows of a SIMD map
-constexpr int MAP_COLS = 3;            // waves run, wrong words, summed wall_clock64 ticks
 constexpr int BLOCKS_PER_CU = 2;       // the default grid of every part
 constexpr int MAX_ITERS = 1 << 16;
 constexpr int MAX_BLOCKS = 8192;       // the store regions of the largest grid: 138 MB
@@ -53,39 +53,9 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-struct Report {
-  unsigned long long errors;   // wrong words (bytes, in the image check)
-  unsigned long long claimed;  // 1 once a lane has written the record below
-  unsigned long long where;    // SIMD map row << 32 | lane << 8 | chain   (walks; the row alone elsewhere)
-  unsigned long long index;    // the part's own index: slice << 32 | word; byte offset; form step
-  unsigned long long got, want;
-};
-
-__device__ __forceinline__ unsigned simd_row() {
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);  // HW_ID; SIMD_ID = bits 5:4
-  return (wave_slot() << 2) | ((hw >> 4) & 3u);                              // < SLOTS
-}
-
-// The end of every kernel, on every lane: a lane with wrong words adds them; one of them in the launch writes the
-// record of its first; lane 0 adds its wave to its SIMD's row.  Vector stores and vector atomics only.
-__device__ __forceinline__ void report(Report* rep, unsigned long long* simd_map, unsigned row, unsigned nbad,
-                                       unsigned long long where_low, unsigned long long index, unsigned long long got,
-                                       unsigned long long want, unsigned long long dt) {
-  unsigned long long* r = simd_map + MAP_COLS * row;
-  if (nbad) {
-    atomicAdd(r + 1, static_cast<unsigned long long>(nbad));
-    atomicAdd(&rep->errors, static_cast<unsigned long long>(nbad));
-    if (atomicCAS(&rep->claimed, 0ULL, 1ULL) == 0ULL) {
-      rep->where = (static_cast<unsigned long long>(row) << 32) | where_low;
-      rep->index = index;
-      rep->got = got;
-      rep->want = want;
-    }
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    atomicAdd(r, 1ULL);
-    atomicAdd(r + 2, dt);
-  }
+// a record's `where`: SIMD map row << 32 | lane << 8 | chain  (walks; the lane alone elsewhere; 0xffff: no lane)
+__device__ __forceinline__ unsigned long long where_of(unsigned row, unsigned low) {
+  return (static_cast<unsigned long long>(row) << 32) | low;
 }
 
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -271,7 +241,7 @@ __global__ void __launch_bounds__(THREADS) walk_kernel(uint8_t* mem, uint32_t me
   const unsigned row = simd_row();
   if (STORE && lane == 0) wave_row[wave] = row;
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, row, nbad, (static_cast<unsigned long long>(lane) << 8) | first_chain, wave, got, want, dt);
+  report(rep, simd_map, row, nbad, where_of(row, (static_cast<unsigned>(lane) << 8) | first_chain), wave, got, want, dt);
 }
 
 // the stores' regions before a walk: every wave's gets the background image
@@ -291,14 +261,8 @@ __global__ void __launch_bounds__(THREADS) check_regions_kernel(const uint32_t* 
     const unsigned nbad = !!(diff & 0xffu) + !!(diff & 0xff00u) + !!(diff & 0xff0000u) + !!(diff & 0xff000000u);
     const uint32_t wave = i / (VMEM_REGION / 4);
     const unsigned row = wave_row[wave];
-    atomicAdd(simd_map + MAP_COLS * row + 1, static_cast<unsigned long long>(nbad));
-    atomicAdd(&rep->errors, static_cast<unsigned long long>(nbad));
-    if (atomicCAS(&rep->claimed, 0ULL, 1ULL) == 0ULL) {
-      rep->where = (static_cast<unsigned long long>(row) << 32) | 0xffffu;  // no lane: a byte of the image
-      rep->index = (static_cast<unsigned long long>(wave) << 32) | (4u * (i % (VMEM_REGION / 4)));
-      rep->got = g;
-      rep->want = w;
-    }
+    const unsigned long long index = (static_cast<unsigned long long>(wave) << 32) | (4u * (i % (VMEM_REGION / 4)));
+    report_wrong(rep, simd_map, row, nbad, where_of(row, 0xffffu), index, g, w);  // no lane: a byte of the image
   }
 }
 
@@ -428,7 +392,7 @@ __global__ void __launch_bounds__(THREADS) bounds_kernel(uint32_t* buf, uint32_t
     }
   const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, row, nbad, static_cast<unsigned long long>(lane) << 8, first, got, want, dt);
+  report(rep, simd_map, row, nbad, where_of(row, lane << 8), first, got, want, dt);
 }
 
 template <int ROW, bool STORE>
@@ -476,8 +440,8 @@ __global__ void __launch_bounds__(THREADS) l1_kernel(const uint32_t* slices, uin
     }
   const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, row, nbad, static_cast<unsigned long long>(lane) << 8,
-         (static_cast<unsigned long long>(slice) << 32) | first, got, want, dt);
+  report(rep, simd_map, row, nbad, where_of(row, lane << 8), (static_cast<unsigned long long>(slice) << 32) | first, got, want,
+         dt);
 }
 
 __global__ void __launch_bounds__(THREADS) fill_slices_kernel(uint32_t* slices, uint32_t slice_words, uint32_t seed) {
@@ -537,7 +501,7 @@ __global__ void __launch_bounds__(THREADS) ldsdma_kernel(const uint8_t* table, u
   }
   const unsigned row = simd_row();
   const unsigned long long dt = static_cast<unsigned long long>(wall_clock64() - t0);
-  report(rep, simd_map, row, nbad, static_cast<unsigned long long>(lane) << 8, first, got, want, dt);
+  report(rep, simd_map, row, nbad, where_of(row, lane << 8), first, got, want, dt);
 }
 
 template <int FORM>
@@ -556,54 +520,11 @@ constexpr hipError_t (*DMA_ATTRIBUTES[DMA_FORMS])(hipFuncAttributes*) = {attribu
 
 // --- host ------------------------------------------------------------------------------------------------------
 // -3 with a message when a kernel was built with scratch, or with another LDS allocation than it may have
-int refuse_memory(const hipFuncAttributes& attr, const std::string& what, size_t lds_allowed = 0) {
-  if (attr.localSizeBytes == 0 && attr.sharedSizeBytes == lds_allowed) return 0;
-  g_err = "vmem test: the kernel of " + what + " was built with " + std::to_string(attr.localSizeBytes) +
-          " bytes of scratch per lane and " + std::to_string(attr.sharedSizeBytes) + " bytes of LDS (allowed: 0 and " +
-          std::to_string(lds_allowed) + "): it would test another memory than the one it names";
-  return -3;
+int refuse(const hipFuncAttributes& attr, const std::string& what, size_t lds_allowed = 0) {
+  return refuse_memory("vmem test", what, attr,
+                       " (allowed: 0 and " + std::to_string(lds_allowed) + "): it would test another memory than the one it names",
+                       lds_allowed);
 }
-
-// the device buffers every part needs, and one checked, timed launch
-struct Run {
-  DevBuf drep, dmap;
-  Timer tm;
-  int open(int device) {
-    HIP_CHECK(drep.alloc(device, sizeof(Report)));
-    HIP_CHECK(dmap.alloc(device, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-    HIP_CHECK(hipMemset(dmap.ptr, 0, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long)));
-    HIP_CHECK(tm.create());
-    return 0;
-  }
-  Report* rep() const { return static_cast<Report*>(drep.ptr); }
-  unsigned long long* map() const { return static_cast<unsigned long long*>(dmap.ptr); }
-  int clear() {
-    HIP_CHECK(hipMemset(drep.ptr, 0, sizeof(Report)));
-    return 0;
-  }
-  // the time of what `enqueue` queues; the report is read by collect()
-  template <typename F>
-  int launch(F&& enqueue, float* ms) {
-    const auto go = [&] {
-      enqueue();
-      return 0;
-    };
-    return tm.timed(go, ms);
-  }
-  // adds the wrong words since clear() to *errors and keeps the first record seen: rec[0..4) = where, index, got, want
-  int collect(unsigned long long* errors, unsigned long long* rec) {
-    Report h;
-    HIP_CHECK(hipMemcpy(&h, drep.ptr, sizeof h, hipMemcpyDeviceToHost));
-    *errors += h.errors;
-    if (h.claimed && rec[0] == ~0ULL) rec[0] = h.where, rec[1] = h.index, rec[2] = h.got, rec[3] = h.want;
-    return 0;
-  }
-  int read_map(unsigned long long* simd_map) {
-    HIP_CHECK(hipMemcpy(simd_map, dmap.ptr, static_cast<size_t>(SLOTS) * MAP_COLS * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
 
 unsigned grid_of(int device, int blocks) {
   return blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
@@ -622,7 +543,7 @@ const char* vmem_last_error(void) { return g_err.c_str(); }
 
 int vmem_device_count(void) { return device_count(); }
 
-int vmem_slots(void) { return SLOTS; }  // rows of every simd_map below
+int vmem_slots(void) { return SIMD_ROWS; }  // rows of every simd_map below
 
 int vmem_ops(void) { return VMEM_OPS; }  // the op table's length; the first vmem_loads() of them are loads
 
@@ -677,9 +598,8 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
     g_err = "vmem walks: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16, reps >= 1 and a list of distinct known ops";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = grid_of(device, blocks);
   *blocks_run = static_cast<int>(grid);
   if (!hook_listed || grid > static_cast<unsigned>(MAX_BLOCKS) ||
@@ -717,7 +637,7 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
     const bool store = vmem_is_store(k);
     hipFuncAttributes attr;
     HIP_CHECK(AllOps::attributes[k](&attr));
-    if (const int rc = refuse_memory(attr, VMEM_OP_TABLE[k].name)) return rc;
+    if (const int rc = refuse(attr, VMEM_OP_TABLE[k].name)) return rc;
     const uint32_t op_seed = vmem_op_seed(seed, k);
     vmem_expected(k, op_seed, iters, -1, reinterpret_cast<const uint8_t*>(table.data()), expect.data(), image.data(), nullptr);
     HIP_CHECK(hipMemcpy(dexp.ptr, expect.data(), expect.size() * 4, hipMemcpyHostToDevice));
@@ -760,7 +680,6 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
     ms[k] = total_ms / reps;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -783,9 +702,8 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
     g_err = "vmem bounds: need a valid device, blocks 0..8192 (0: 2 per CU) and n a power of two from 1 KiB to 64 KiB";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = grid_of(device, blocks);
   *blocks_run = static_cast<int>(grid);
   if (grid > static_cast<unsigned>(MAX_BLOCKS)) {
@@ -814,7 +732,7 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
       const bool structured = row >= 2, x4 = row & 1;
       hipFuncAttributes attr;
       HIP_CHECK(BOUNDS_ATTRIBUTES[store][row](&attr));
-      if (const int rc = refuse_memory(attr, "a bounds row")) return rc;
+      if (const int rc = refuse(attr, "a bounds row")) return rc;
       if (store) {  // the model's image of one wave: the background, then the in-range lanes' words
         image = fill;
         for (uint32_t kk = 0; kk < vmem_bounds_rounds(n); ++kk)
@@ -827,16 +745,14 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
       }
       for (int r = 0; r < 2; ++r) {  // r == 0: the warm-up, which carries the hook
         const uint32_t covered = (structured ? n / VMEM_STRIDE : n) * (r == 0 && leak ? 2u : 1u);
-        if (const int rc = run.clear()) return rc;
         if (store)
           for (uint32_t w = 0; w < waves; ++w)
             HIP_CHECK(hipMemcpyAsync(static_cast<uint32_t*>(dstore.ptr) + static_cast<size_t>(w) * words, fill.data(),
                                      static_cast<size_t>(words) * 4, hipMemcpyHostToDevice, nullptr));
         float t = 0.f;
         uint32_t* buf = static_cast<uint32_t*>(store ? dstore.ptr : dload.ptr);
-        if (const int rc = run.launch([&] { BOUNDS_LAUNCH[store][row](grid, buf, n, covered, seed32, run.rep(), run.map()); }, &t))
-          return rc;
-        if (const int rc = run.collect(errors + k, first + 4 * k)) return rc;
+        const auto enqueue = [&] { BOUNDS_LAUNCH[store][row](grid, buf, n, covered, seed32, run.rep(), run.map()); };
+        if (const int rc = run.checked(enqueue, &t, errors + k, first + 4 * k)) return rc;
         if (store) {
           HIP_CHECK(hipMemcpy(back.data(), dstore.ptr, back.size() * 4, hipMemcpyDeviceToHost));
           for (uint32_t w = 0; w < waves; ++w)
@@ -853,7 +769,6 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
       }
     }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -876,9 +791,8 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
             "1 MiB and passes 1..65536";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = grid_of(device, blocks);
   *blocks_run = static_cast<int>(grid);
   const uint32_t slice_words = slice_bytes / 4;
@@ -892,9 +806,9 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
   *ms_plain = *ms_sc1 = 0.0;
   hipFuncAttributes attr;
   HIP_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(l1_kernel<false>)));
-  if (const int rc = refuse_memory(attr, "the L1 walk")) return rc;
+  if (const int rc = refuse(attr, "the L1 walk")) return rc;
   HIP_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(l1_kernel<true>)));
-  if (const int rc = refuse_memory(attr, "the L1 walk with sc1")) return rc;
+  if (const int rc = refuse(attr, "the L1 walk with sc1")) return rc;
   Run run;
   if (const int rc = run.open(device)) return rc;
   const uint32_t seed32 = vmem_mix32(seed);
@@ -911,14 +825,12 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
       const bool hooked = r == 0 && hooked_word;
       if (hooked)
         if (const int rc = flip_word_bit(hooked_word)) return rc;
-      if (const int rc = run.clear()) return rc;
       float t = 0.f;
       const auto enqueue = [&] {
         if (sc1) hipLaunchKernelGGL(l1_kernel<true>, dim3(grid), dim3(THREADS), 0, nullptr, slices, slice_words, seed32, passes, run.rep(), run.map());
         else hipLaunchKernelGGL(l1_kernel<false>, dim3(grid), dim3(THREADS), 0, nullptr, slices, slice_words, seed32, passes, run.rep(), run.map());
       };
-      if (const int rc = run.launch(enqueue, &t)) return rc;
-      if (const int rc = run.collect(errors, first)) return rc;
+      if (const int rc = run.checked(enqueue, &t, errors, first)) return rc;
       if (hooked)
         if (const int rc = flip_word_bit(hooked_word)) return rc;
       if (r > 0) total_ms += t;
@@ -926,7 +838,6 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
     *(sc1 ? ms_sc1 : ms_plain) = total_ms / reps;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -946,9 +857,8 @@ int vmem_ldsdma(int device, int blocks, int iters, int reps, uint64_t seed, unsi
     g_err = "vmem ldsdma: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16 and reps >= 1";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   const unsigned grid = grid_of(device, blocks);
   *blocks_run = static_cast<int>(grid);
   for (int f = 0; f < DMA_FORMS; ++f) {
@@ -968,23 +878,20 @@ int vmem_ldsdma(int device, int blocks, int iters, int reps, uint64_t seed, unsi
   for (int f = 0; f < DMA_FORMS; ++f) {
     hipFuncAttributes attr;
     HIP_CHECK(DMA_ATTRIBUTES[f](&attr));
-    if (const int rc = refuse_memory(attr, DMA_NAMES[f], (THREADS / 64) * 1024)) return rc;
+    if (const int rc = refuse(attr, DMA_NAMES[f], (THREADS / 64) * 1024)) return rc;
     double total_ms = 0.0;
     for (int r = 0; r <= reps; ++r) {
-      if (const int rc = run.clear()) return rc;
       float t = 0.f;
       const auto enqueue = [&] {
         DMA_LAUNCH[f](grid, static_cast<const uint8_t*>(dtable.ptr), table_seed, vmem_op_seed(seed, 1000 + f + 16 * r), iters,
                       run.rep(), run.map());
       };
-      if (const int rc = run.launch(enqueue, &t)) return rc;
-      if (const int rc = run.collect(errors + f, first + 4 * f)) return rc;
+      if (const int rc = run.checked(enqueue, &t, errors + f, first + 4 * f)) return rc;
       if (r > 0) total_ms += t;
     }
     ms[f] = total_ms / reps;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 
@@ -1019,12 +926,11 @@ int vmem_apply(int device, int op, int n, const unsigned int* mem_words, unsigne
             "otherwise, and a descriptor inside the memory";
     return -2;
   }
-  int cur = 0;
-  HIP_CHECK(hipGetDevice(&cur));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  if (const int rc = scope.enter(device)) return rc;
   hipFuncAttributes attr;
   HIP_CHECK(AllOps::apply_attributes[op](&attr));
-  if (const int rc = refuse_memory(attr, std::string("apply of ") + VMEM_OP_TABLE[op].name)) return rc;
+  if (const int rc = refuse(attr, std::string("apply of ") + VMEM_OP_TABLE[op].name)) return rc;
   const size_t rows = static_cast<size_t>(n) * VMEM_WAVE;
   DevBuf dmem, doff, dregs, dout;
   HIP_CHECK(dmem.alloc(device, static_cast<size_t>(nwords) * 4));
@@ -1041,7 +947,6 @@ int vmem_apply(int device, int op, int n, const unsigned int* mem_words, unsigne
   HIP_CHECK(hipDeviceSynchronize());
   if (vmem_is_store(op)) HIP_CHECK(hipMemcpy(out, dmem.ptr, static_cast<size_t>(nwords) * 4, hipMemcpyDeviceToHost));
   else HIP_CHECK(hipMemcpy(out, dout.ptr, rows * 16, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipSetDevice(cur));
   return 0;
 }
 

@@ -810,6 +810,13 @@ def simd_name(row: int) -> str:
     return f"{slot_name(row >> 2)}/simd{row & 3}"
 
 
+def simd_map_summary(m: Sequence[int], nrows: int) -> Tuple[List[int], int, List[str]]:
+    """What the opt-in diagnostics report of a SIMD map of ``nrows`` x 3 (waves run, wrong words, ticks): the rows
+    that ran a wave, how many XCDs they lie on, and ``name (wrong words)`` of every row with wrong words."""
+    seen = [r for r in range(nrows) if m[3 * r]]
+    return seen, len({r >> 9 for r in seen}), [f"{simd_name(r)} ({m[3 * r + 1]})" for r in seen if m[3 * r + 1]]
+
+
 def regfile_test(device: int = 0, rounds: int = 2, seed: int = 0x51D, hold: int = 32, inject_block: int = -1,
                  inject_reg: str = "vgpr_lo") -> Dict[str, Any]:
     """Both vector register files of every SIMD (256 VGPRs + 256 AGPRs x 64 lanes = 128 KiB) under four patterns,

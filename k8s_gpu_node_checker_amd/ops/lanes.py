@@ -21,6 +21,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+from .diag import simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
 from .native import load_cdll
 
 # the native op index (LanesOp of lanes_ref.h): index into this
@@ -82,13 +83,6 @@ def device_count() -> int:
     return int(lib().lanes_device_count())
 
 
-def simd_name(row: int) -> str:
-    """``xcd3/se1/cu5/simd2`` of a SIMD map row (``wave_slot() << 2 | HW_ID.SIMD_ID``, as the register-file test's)."""
-    slot = row >> 2
-    return (f"xcd{slot >> 7}/se{(slot >> 5) & 3}/cu{slot & 15}" + ("/sh1" if (slot >> 4) & 1 else "")
-            + f"/simd{row & 3}")
-
-
 def lanes_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = 2000, reps: int = 5,
                blocks: Optional[int] = None, seed: int = DEFAULT_SEED, inject_op: Optional[str] = None,
                inject_block: int = -1, inject_skip_iter: int = -1, slots: bool = False) -> Dict[str, Any]:
@@ -140,11 +134,10 @@ def lanes_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = 2000, rep
                    "gops": float(f"{crossings / (ms[i] * 1e-3) / 1e9:.4g}") if ms[i] > 0 else 0.0}
         if errs[i]:
             problems.append(f"{errs[i]} wrong lanes in {k}" + (f" on {bad['where']}" if bad else ""))
-    seen = [r for r in range(nrows) if m[3 * r]]
-    bad_simds = [f"{simd_name(r)} ({m[3 * r + 1]})" for r in seen if m[3 * r + 1]]
+    seen, xcds, bad_simds = simd_map_summary(m, nrows)
     total = sum(r["errors"] for r in rows.values())
     res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen),
-                           "xcds": len({r >> 9 for r in seen}), "blocks": ran.value, "iters": int(iters),
+                           "xcds": xcds, "blocks": ran.value, "iters": int(iters),
                            "ops": rows, "ms": round(sum(r["ms"] for r in rows.values()), 4),
                            "wall_s": round(time.perf_counter() - t0, 3), "detail": "; ".join(problems[:4])
                            + (" ..." if len(problems) > 4 else "")}

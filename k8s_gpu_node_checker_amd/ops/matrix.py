@@ -22,6 +22,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+from .diag import simd_map_summary
 from .lanes import simd_name
 from .native import load_cdll
 
@@ -156,11 +157,10 @@ def matrix_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_
                    "tops": float(f"{work / (ms[i] * 1e-3) / 1e12:.4g}") if ms[i] > 0 else 0.0}
         if errs[i]:
             problems.append(f"{errs[i]} wrong elements in {k}" + (f" on {bad['where']}" if bad else ""))
-    seen = [r for r in range(nrows) if m[3 * r]]
-    bad_simds = [f"{simd_name(r)} ({m[3 * r + 1]})" for r in seen if m[3 * r + 1]]
+    seen, xcds, bad_simds = simd_map_summary(m, nrows)
     total = sum(r["errors"] for r in rows.values())
     res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen),
-                           "xcds": len({r >> 9 for r in seen}), "blocks": ran.value, "iters": int(iters),
+                           "xcds": xcds, "blocks": ran.value, "iters": int(iters),
                            "ops": rows, "ms": round(sum(r["ms"] for r in rows.values()), 4),
                            "wall_s": round(time.perf_counter() - t0, 3), "detail": "; ".join(problems[:4])
                            + (" ..." if len(problems) > 4 else "")}

@@ -26,6 +26,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+from .diag import simd_map_summary, simd_name
 from .native import load_cdll
 
 # the native op index (ScalarOp of scalar_ref.h): index into this
@@ -110,13 +111,6 @@ def _check(rc: int) -> None:
 
 def device_count() -> int:
     return int(lib().scalar_device_count())
-
-
-def simd_name(row: int) -> str:
-    """``xcd3/se1/cu5/simd2`` of a SIMD map row (``wave_slot() << 2 | HW_ID.SIMD_ID``, as the register-file test's)."""
-    slot = row >> 2
-    return (f"xcd{slot >> 7}/se{(slot >> 5) & 3}/cu{slot & 15}" + ("/sh1" if (slot >> 4) & 1 else "")
-            + f"/simd{row & 3}")
 
 
 def sgpr_range() -> Dict[str, Any]:
@@ -281,10 +275,9 @@ def scalar_test(device: int = 0, parts: Sequence[str] = PARTS, ops: Sequence[str
                              "ms": round(sum(r["ms"] for r in rows.values()), 4), "small_bytes": int(small_bytes),
                              "large_bytes": int(large_bytes), "passes": int(passes), "loads": int(loads), "kinds": rows}
 
-    seen = [r for r in range(nrows) if total_map[3 * r]]
-    bad_simds = [f"{simd_name(r)} ({total_map[3 * r + 1]})" for r in seen if total_map[3 * r + 1]]
+    seen, xcds, bad_simds = simd_map_summary(total_map, nrows)
     total = sum(p["errors"] for p in out_parts.values())
-    res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen), "xcds": len({r >> 9 for r in seen}),
+    res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen), "xcds": xcds,
                            "blocks": grids, "parts": out_parts, "ms": round(sum(p["ms"] for p in out_parts.values()), 4),
                            "wall_s": round(time.perf_counter() - t0, 3),
                            "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}

@@ -33,6 +33,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+from .diag import simd_map_summary
 from .lanes import simd_name
 from .native import load_cdll
 
@@ -271,18 +272,17 @@ def vmem_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_IT
     ldsdma = {"errors": sum(r["errors"] for r in frows.values()), "ms": round(sum(r["ms"] for r in frows.values()), 4),
               "iters": int(iters), "forms": frows}
 
-    seen = [r for r in range(nrows) if total_map[3 * r]]
-    bad_rows = [r for r in seen if total_map[3 * r + 1]]
+    seen, xcds, bad_simds = simd_map_summary(total_map, nrows)
     total = sum(r["errors"] for r in rows.values()) + bounds["errors"] + l1["errors"] + ldsdma["errors"]
-    res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen), "xcds": len({r >> 9 for r in seen}),
+    res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen), "xcds": xcds,
                            "blocks": grid, "iters": int(iters), "ops": rows, "bounds": bounds, "l1": l1, "ldsdma": ldsdma,
                            "ms": round(sum(r["ms"] for r in rows.values()) + bounds["ms"] + l1["ms"] + l1["ms_sc1"]
                                        + ldsdma["ms"], 4),
                            "wall_s": round(time.perf_counter() - t0, 3),
                            "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_rows:
-        res["bad_simds"] = [f"{simd_name(r)} ({total_map[3 * r + 1]})" for r in bad_rows]
-        res["bad_cus"] = sorted({cu_name(r) for r in bad_rows})
+    if bad_simds:
+        res["bad_simds"] = bad_simds
+        res["bad_cus"] = sorted({cu_name(r) for r in seen if total_map[3 * r + 1]})
     if slots:
         res["slots"] = seen
     return res

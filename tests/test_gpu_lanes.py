@@ -178,6 +178,29 @@ def test_refused_calls(lanes):
             lanes.lanes_test(0, **kw)
 
 
+def test_a_call_on_another_device_leaves_the_threads_device_as_it_was(lanes):
+    """Refused after the library has made the other device current, and passing: either way the calling thread's HIP
+    device is the one it had.  The refused call launches nothing."""
+    import ctypes
+    if lanes.device_count() < 2:
+        pytest.skip("needs two devices")
+    hip = ctypes.CDLL("libamdhip64.so")  # the runtime the library has loaded
+
+    def current():
+        dev = ctypes.c_int(-1)
+        assert hip.hipGetDevice(ctypes.byref(dev)) == 0
+        return dev.value
+
+    before = current()
+    other = 0 if before == 1 else 1
+    with pytest.raises(RuntimeError, match=r"lanes failed \(-2\)"):
+        lanes.lanes_test(other, blocks=4, iters=1, reps=1, inject_op="readlane", inject_block=4)
+    assert current() == before
+    r = lanes.lanes_test(other, blocks=1, iters=1, reps=1)
+    assert r["pass"] and r["errors"] == 0, r
+    assert current() == before
+
+
 def test_the_cli_flag_carries_a_passing_lanes_result(repo):
     def run(*flags):
         p = subprocess.run([sys.executable, "-m", "k8s_gpu_node_checker_amd.ops.diag", "--level", "1", "--device", "0",
