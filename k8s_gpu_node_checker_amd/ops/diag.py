@@ -161,6 +161,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "matrix": "34ops-steps4-exact-r1",  # no rate verdict either (ops/matrix.py): which ops a clean result covered
     # no rate verdict either (ops/vmem.py): the load / store ops, bounds rows and LDS-DMA forms a clean result covered
     "vmem": "36loads+23stores-chains4+8bounds+l1+4ldsdma-r1",
+    # no rate verdict either (ops/cvt.py): the op groups a clean result covered (the ops themselves: cvt.OPS)
+    "cvt": "classic+bf16+fp8+scalef32-chains4-r1",
 }
 
 
@@ -886,6 +888,14 @@ def vmem_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return vmem.vmem_test(device, **kw)
 
 
+def cvt_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in cvt diagnostic (``ops/cvt.cvt_test``, its own library): every format conversion of the vector ALU
+    (classic, bf16, fp8 / bf8, the gfx950 scalef32 forms) as one native instruction in chains that every lane checks
+    bit for bit against the host's model.  No level runs it; ``run(extra=("cvt",))`` does."""
+    from . import cvt  # lazily: only who asks for the test needs libmi355x_cvt.so
+    return cvt.cvt_test(device, **kw)
+
+
 def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in lanes diagnostic (``ops/lanes.lanes_test``, its own library): every lane-crossing instruction of a
     wave (DPP, the permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane / readfirstlane) in chains that
@@ -1208,10 +1218,11 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "scalar": ("scalar_test", {}),  # in no level: run(extra=("scalar",))
     "matrix": ("matrix_test", {}),  # in no level: run(extra=("matrix",))
     "vmem": ("vmem_test", {}),  # in no level: run(extra=("vmem",))
+    "cvt": ("cvt_test", {}),  # in no level: run(extra=("cvt",))
 }
 # error counts only: nothing to scale
 _UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test"))
+                       "vmem_test", "cvt_test"))
 
 
 def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
@@ -1274,7 +1285,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``),
     each treated as the level's own are.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
@@ -1360,6 +1371,12 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
                 f"{len(b.get('rows') or {})} bounds rows, L1 {l1.get('slice_bytes', '?')} B x {l1.get('passes', '?')} passes "
                 f"(sc1 / plain {l1.get('l1_gain', 0):.2f}), {len(dma.get('forms') or {})} LDS-DMA forms, "
                 f"{r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
+    if test == "cvt":
+        rows, mode = r.get("ops") or {}, r.get("mode") or {}
+        rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
+        return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+                f"XCDs, round {mode.get('round', '?')} denorm {mode.get('denorm', '?')}, {r.get('errors', 0)} wrong words; "
+                f"{r.get('ms', 0):.1f} ms, mean {rate:.0f} G conversions/s")
     if test == "scalar":
         p = r.get("parts") or {}
         salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
@@ -1560,7 +1577,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1595,6 +1612,10 @@ def main(argv=None) -> int:
                     help="also run the vmem diagnostic on every device: every vector load and store form against the "
                          "host's model, the buffer descriptor's range check, the vector L1 of every CU and the "
                          "LDS-DMA loads (ops/vmem.py)")
+    ap.add_argument("--cvt", action="store_true",
+                    help="also run the cvt diagnostic on every device: every format conversion of the vector ALU "
+                         "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
+                         "wrong words located to their SIMD (ops/cvt.py)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1609,7 +1630,7 @@ def main(argv=None) -> int:
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
     opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
-                                             ("matrix", args.matrix), ("vmem", args.vmem))
+                                             ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt))
                    if on)
     more = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.duration > 0:

@@ -1,5 +1,5 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
-``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so`` and
+``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so`` and
 ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
@@ -666,6 +666,126 @@ class FakeLanesLib:
         return -1
 
 
+def cvt_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeCvtLib` stands in for, read from csrc/cvt/cvt.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "cvt", "cvt.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(cvt_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+def cvt_c_ops() -> List[str]:
+    """The op names of csrc/cvt/cvt_ref.h's table, in order."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "cvt", "cvt_ref.h")) as f:
+        return re.findall(r'^\s*X\((\w+), "v_cvt_\w+", CG_', f.read(), re.M)
+
+
+class FakeCvtLib:
+    """``libmi355x_cvt.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD, the waves in
+    float mode ``mode`` (MODE bits 7:0; 0xf0: round-to-nearest-even, denormals kept).
+
+    bad:      ``{(device, op index): wrong words}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the
+              first of them lane 9, chain 1, read as ``want ^ 0x100``
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``cvt{device}`` in ``calls``: empty = never called."""
+
+    OPS = len(cvt_c_ops())  # the op table's length, read from cvt_ref.h: nothing repeats the count
+    SLOTS = 4096
+    WANT = 0x5EEDC0A7
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
+                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 mode: int = 0xf0, physical: Optional[int] = None):
+        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
+        self.float_mode, self.physical = mode, physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def cvt_last_error(self) -> bytes:
+        return self.err
+
+    def cvt_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def cvt_slots(self) -> int:
+        return self.SLOTS
+
+    def cvt_ops(self) -> int:
+        return self.OPS
+
+    def cvt_row_words(self, op, operand_words, result_words):
+        self.err = b"cvt row_words: the stand-in has no model"
+        return -1
+
+    def cvt_shape_rows(self, op, seed, n, rows):
+        self.err = b"cvt shape_rows: the stand-in has no model"
+        return -1
+
+    def cvt_model_rows(self, op, rows, n, out, ok):
+        self.err = b"cvt model_rows: the stand-in has no model"
+        return -1
+
+    def cvt_test(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
+                 errors, first, ms, mode, simd_map, blocks_run):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"cvt{device}")
+        chosen = [ops[i] for i in range(nops)] if 1 <= nops <= self.OPS else []
+        if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 16 or reps < 1 or not chosen \
+                or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
+            self.err = (b"cvt test: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^16, reps >= 1 and a list "
+                        b"of distinct known ops")
+            return -2
+        grid = blocks or self.xcds * 32 * 4
+        _put(blocks_run, ctypes.c_int, grid)
+        if (inject_op >= 0 and (inject_op not in chosen or not 0 <= inject_block < grid or inject_skip_iter >= iters)):
+            self.err = b"cvt test: inject_op must be in the list, inject_block inside the grid and inject_skip_iter below iters"
+            return -2
+        _put(mode, ctypes.c_uint, self.float_mode)
+        if self.float_mode & 0xff != 0xf0:
+            field = b"FP_ROUND" if self.float_mode & 0xf else b"FP_DENORM"
+            self.err = b"cvt test: the waves run with MODE." + field + b": the model holds for another"
+            return -3
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        launches = (reps + 1) * len(chosen)
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = 1000 * iters * launches
+        for k in range(self.OPS):
+            on = k in chosen
+            wrong = self.bad.get((device, k), 0) if on else 0
+            if on and k == inject_op:
+                wrong += 1
+            errors[k] = wrong
+            first[4 * k] = ((self.bad_row << 16) | (9 << 8) | 1) if wrong else (1 << 64) - 1
+            first[4 * k + 1] = 0
+            first[4 * k + 2] = self.WANT ^ 0x100 if wrong else 0
+            first[4 * k + 3] = self.WANT if wrong else 0
+            ms[k] = self.ms if on else 0.0
+            if wrong:
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+        return 0
+
+    def cvt_apply_many(self, device, op, rows, nrows, out):
+        self.err = b"cvt apply: the stand-in has no wave to apply an instruction on"
+        return -1
+
+
 def matrix_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1300,9 +1420,9 @@ class NarrowedDiagLib:
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
-            vmem: Optional[Dict] = None, **diag_kw) -> None:
+            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1335,3 +1455,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import vmem as vmem_mod
     vlib = FakeVmemLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(vmem or {}))
     vmem_mod.lib = lambda: vlib
+    from ..ops import cvt as cvt_mod
+    clib = FakeCvtLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(cvt or {}))
+    cvt_mod.lib = lambda: clib
