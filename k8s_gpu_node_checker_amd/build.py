@@ -88,7 +88,7 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "headers": [os.path.join(CSRC, "diag", h) for h in (
                 "types.h", "tile_order.h", "gemm_epilogue.h", "gemm_kernels.h", "gemm_common.h", "gemm_v1.h", "gemm_v2.h",
                 "gemm_v3.h", "gemm_v4.h", "v4_plan.h", "gemm_check.h", "mem_kernels.h", "burn_kernels.h",
-                "valu_ref.h", "xcd_kernels.h", "gemm_host.h")] + [hip_host],
+                "valu_ref.h", "xcd_kernels.h", "gemm_host.h", "gemm_verdict.h")] + [hip_host],
             "out": os.path.join(OUT, "libmi355x_diag.so"),
             "cmd": hip_cmd,
             "requires": hipcc,

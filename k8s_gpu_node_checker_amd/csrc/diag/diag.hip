@@ -38,8 +38,8 @@
 //
 // This file holds the entry points (every extern "C" block) and the runners only they use.  The kernels are in
 // gemm_kernels.h (gemm_common.h and gemm_v1.h to gemm_v4.h, one GEMM generation each, on tile_order.h and v4_plan.h),
-// gemm_check.h, mem_kernels.h, burn_kernels.h and xcd_kernels.h, the GEMM launch dispatch in gemm_host.h, the host
-// helpers shared with the other libraries in ../common/hip_host.h.
+// gemm_check.h, mem_kernels.h, burn_kernels.h and xcd_kernels.h, the GEMM launch dispatch in gemm_host.h, the HIP-free
+// half of the GEMM verdict in gemm_verdict.h, the host helpers shared with the other libraries in ../common/hip_host.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -328,44 +328,88 @@ struct GemmFp8 {
   static TileGeom geom(int, int) { return kGeomV3; }
 };
 
-// Self-contained MFMA burn-in: allocate, fill, run `iters` GEMMs, time them, verify `nsamp` sampled outputs
-// against the reference kernel and, with ck_tol >= 0, every output by tile checksums (gemm_checksum:
-// *ck_err, ck_out[kCkOut], *ck_floor).  `inject_elem` >= 0 overwrites that output between the timing and the
-// checks: with 1e6, or (inject_delta not NaN) with its own value plus inject_delta.  The shape is the caller's to check.
+// Optional host copies of what gemm_verify judged (any pointer may be null): the sample positions, the sampled
+// reference and magnitude (zeros where the type forms none) and the checksums' per-(row block, column) arrays.
+struct VerifyOut {
+  int *rows = nullptr, *cols = nullptr;
+  double *ref = nullptr, *mag = nullptr, *ck_ref = nullptr, *ck_mag = nullptr, *ck_csum = nullptr;
+};
+
+// The referee of a diagnostic run, on device buffers the caller owns: `nsamp` sampled outputs of C against the
+// reference kernel (*max_err) and, with ck_tol >= 0, every output by tile checksums over the tiles `g`
+// (gemm_checksum: *ck_err, ck_out[kCkOut], *ck_floor).  `cs` != NULL: C is bf16 and cs the fused csum[M / 128][N];
+// NULL: C is fp32.  The shape is the caller's to check.
 template <typename T>
-int gemm_run(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
-             double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
-             long long* ck_out, double* ck_floor) {
+int gemm_verify(int device, const void* A, const void* Bt, const void* Cv, const double* cs, int M, int N, int K,
+                TileGeom g, int nsamp, double ck_tol, double* max_err, double* ck_err, long long* ck_out,
+                double* ck_floor, const VerifyOut& vo = VerifyOut()) {
   using Ref = typename T::Ref;
-  HIP_CHECK(hipSetDevice(device));
-  // bf16 C and the kernel's own column sums (OUT_BF16_CK), or fp32 C
-  const bool fused = gemm_fused(T::DT, M, N);
-  DevBuf bA, bBt, bC, bcs, bref, bmag, brows, bcols, bgot;
-  HIP_CHECK(bA.alloc(device, T::kElemBytes * static_cast<size_t>(M) * K));
-  HIP_CHECK(bBt.alloc(device, T::kElemBytes * static_cast<size_t>(N) * K));
-  HIP_CHECK(bC.alloc(device, (fused ? sizeof(__bf16) : sizeof(float)) * static_cast<size_t>(M) * N));
-  if (fused) HIP_CHECK(bcs.alloc(device, sizeof(double) * static_cast<size_t>(M / 128) * N));
+  const bool fused = cs != nullptr;
+  DevBuf bref, bmag, brows, bcols, bgot;
   HIP_CHECK(bref.alloc(device, sizeof(Ref) * nsamp));
   if (T::kMag) HIP_CHECK(bmag.alloc(device, sizeof(double) * nsamp));
   HIP_CHECK(brows.alloc(device, sizeof(int) * nsamp));
   HIP_CHECK(bcols.alloc(device, sizeof(int) * nsamp));
   HIP_CHECK(bgot.alloc(device, sizeof(float) * nsamp));
-  double* cs = static_cast<double*>(bcs.ptr);
-  float* C = static_cast<float*>(bC.ptr);
-  __bf16* Cb = static_cast<__bf16*>(bC.ptr);
   const int* rows = static_cast<const int*>(brows.ptr);
   const int* cols = static_cast<const int*>(bcols.ptr);
   float* got = static_cast<float*>(bgot.ptr);
+  std::vector<int> hr, hc;
+  sample_indices(T::kSampleSeed, nsamp, M, N, hr, hc);
+  HIP_CHECK(hipMemcpy(brows.ptr, hr.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(bcols.ptr, hc.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
+  T::launch_ref(A, Bt, rows, cols, bref.ptr, bmag.ptr, nsamp, K);
+  // gather the sampled outputs on the device: one copy instead of nsamp tiny ones
+  if (fused)
+    hipLaunchKernelGGL(gather_kernel<__bf16>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
+                       static_cast<const __bf16*>(Cv), rows, cols, got, nsamp, N);
+  else
+    hipLaunchKernelGGL(gather_kernel<float>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr,
+                       static_cast<const float*>(Cv), rows, cols, got, nsamp, N);
+  HIP_CHECK(hipGetLastError());
+  std::vector<Ref> href(nsamp);
+  std::vector<double> hmag(nsamp, 0.0);
+  std::vector<float> hC(nsamp);
+  HIP_CHECK(hipMemcpy(href.data(), bref.ptr, sizeof(Ref) * nsamp, hipMemcpyDeviceToHost));
+  if (T::kMag) HIP_CHECK(hipMemcpy(hmag.data(), bmag.ptr, sizeof(double) * nsamp, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(hC.data(), bgot.ptr, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
+  const std::vector<double> ref64(href.begin(), href.end());
+  *max_err = sampled_worst(hC.data(), ref64.data(), hmag.data(), nsamp, fused, T::kMag);
+  if (vo.rows) std::copy(hr.begin(), hr.end(), vo.rows);
+  if (vo.cols) std::copy(hc.begin(), hc.end(), vo.cols);
+  if (vo.ref) std::copy(ref64.begin(), ref64.end(), vo.ref);
+  if (vo.mag) std::copy(hmag.begin(), hmag.end(), vo.mag);
+  if (ck_tol >= 0.0)
+    return gemm_checksum<T::DT>(device, A, Bt, static_cast<const float*>(Cv), M, N, K, g, ck_tol, ck_err, ck_out, cs,
+                                ck_floor, vo.ck_ref, vo.ck_mag, vo.ck_csum);
+  return 0;
+}
+
+// Self-contained MFMA burn-in: allocate, fill, run `iters` GEMMs, time them, then the referee (gemm_verify): `nsamp`
+// sampled outputs against the reference kernel and, with ck_tol >= 0, every output by tile checksums
+// (*ck_err, ck_out[kCkOut], *ck_floor).  `inject_elem` >= 0 overwrites that output between the timing and the
+// checks: with 1e6, or (inject_delta not NaN) with its own value plus inject_delta.  The shape is the caller's to check.
+template <typename T>
+int gemm_run(int device, int M, int N, int K, int warmup, int iters, int nsamp, long long inject_elem,
+             double inject_delta, double ck_tol, double* tflops, double* max_err, double* ms_per_iter, double* ck_err,
+             long long* ck_out, double* ck_floor) {
+  HIP_CHECK(hipSetDevice(device));
+  // bf16 C and the kernel's own column sums (OUT_BF16_CK), or fp32 C
+  const bool fused = gemm_fused(T::DT, M, N);
+  DevBuf bA, bBt, bC, bcs;
+  HIP_CHECK(bA.alloc(device, T::kElemBytes * static_cast<size_t>(M) * K));
+  HIP_CHECK(bBt.alloc(device, T::kElemBytes * static_cast<size_t>(N) * K));
+  HIP_CHECK(bC.alloc(device, (fused ? sizeof(__bf16) : sizeof(float)) * static_cast<size_t>(M) * N));
+  if (fused) HIP_CHECK(bcs.alloc(device, sizeof(double) * static_cast<size_t>(M / 128) * N));
+  double* cs = static_cast<double*>(bcs.ptr);
+  float* C = static_cast<float*>(bC.ptr);
+  __bf16* Cb = static_cast<__bf16*>(bC.ptr);
   auto run = [&]() -> int {
     return fused ? T::launch_ck(bA.ptr, bBt.ptr, Cb, cs, M, N, K) : T::launch_f32(bA.ptr, bBt.ptr, C, M, N, K);
   };
   T::fill(bA.ptr, static_cast<size_t>(M) * K, T::kSeedA);
   T::fill(bBt.ptr, static_cast<size_t>(N) * K, T::kSeedBt);
   HIP_CHECK(hipGetLastError());
-  std::vector<int> hr, hc;
-  sample_indices(T::kSampleSeed, nsamp, M, N, hr, hc);
-  HIP_CHECK(hipMemcpy(brows.ptr, hr.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(bcols.ptr, hc.data(), sizeof(int) * nsamp, hipMemcpyHostToDevice));
   Timer tm;
   HIP_CHECK(tm.create());
   for (int i = 0; i < warmup; ++i)
@@ -380,33 +424,10 @@ int gemm_run(int device, int M, int N, int K, int warmup, int iters, int nsamp, 
   const double ms = t_ms / std::max(iters, 1);
   if (fused) HIP_CHECK(inject_output_ck(Cb, cs, inject_elem, M, N, inject_delta));
   else HIP_CHECK(inject_output(C, inject_elem, static_cast<long long>(M) * N, inject_delta));
-  T::launch_ref(bA.ptr, bBt.ptr, rows, cols, bref.ptr, bmag.ptr, nsamp, K);
-  // gather the sampled outputs on the device: one copy instead of nsamp tiny ones
-  if (fused)
-    hipLaunchKernelGGL(gather_kernel<__bf16>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, Cb, rows, cols, got,
-                       nsamp, N);
-  else
-    hipLaunchKernelGGL(gather_kernel<float>, dim3((nsamp + 255) / 256), dim3(256), 0, nullptr, C, rows, cols, got,
-                       nsamp, N);
-  HIP_CHECK(hipGetLastError());
-  std::vector<Ref> href(nsamp);
-  std::vector<double> hmag(T::kMag ? nsamp : 0);
-  std::vector<float> hC(nsamp);
-  HIP_CHECK(hipMemcpy(href.data(), bref.ptr, sizeof(Ref) * nsamp, hipMemcpyDeviceToHost));
-  if (T::kMag) HIP_CHECK(hipMemcpy(hmag.data(), bmag.ptr, sizeof(double) * nsamp, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hC.data(), bgot.ptr, sizeof(float) * nsamp, hipMemcpyDeviceToHost));
-  double worst = 0.0;
-  for (int i = 0; i < nsamp; ++i) {
-    const double d = fused ? beyond_bf16_rounding(hC[i], href[i]) : std::fabs(static_cast<double>(hC[i]) - href[i]);
-    worst = std::max(worst, std::isnan(d) ? HUGE_VAL : d / T::denom(href[i], T::kMag ? hmag[i] : 0.0));
-  }
-  *max_err = worst;
   *ms_per_iter = ms;
   *tflops = 2.0 * M * N * static_cast<double>(K) / (ms * 1e-3) / 1e12;
-  if (ck_tol >= 0.0)
-    return gemm_checksum<T::DT>(device, bA.ptr, bBt.ptr, C, M, N, K, T::geom(M, N), ck_tol, ck_err, ck_out,
-                                fused ? cs : nullptr, ck_floor);
-  return 0;
+  return gemm_verify<T>(device, bA.ptr, bBt.ptr, bC.ptr, fused ? cs : nullptr, M, N, K, T::geom(M, N), nsamp, ck_tol,
+                        max_err, ck_err, ck_out, ck_floor);
 }
 
 }  // namespace
@@ -446,6 +467,64 @@ int diag_gemm_fp8(int device, int M, int N, int K, int warmup, int iters, int ns
   }
   return gemm_run<GemmFp8>(device, M, N, K, warmup, iters, nsamp, inject_elem, inject_delta, ck_tol, tflops, max_err,
                            ms_per_iter, ck_err, ck_out, ck_floor);
+}
+
+// The diagnostics' referee (gemm_verify) on caller-owned device buffers of the current device, for the tests: dt 0 =
+// bf16, 1 = E4M3 operands A[M][K], Bt[N][K]; geom 0 = 128/128/8 tiles (bf16 only), 1 = 256/256/4.  csum != NULL: C is
+// bf16 and csum the fused csum[M / 128][N] (geom 1 only); NULL: C is fp32.  ck_tol < 0: no checksums (ck_err, ck_out,
+// ck_floor untouched, and they may be null; with checksums ck_floor may still be null).  Optional host arrays, each
+// of which may be null: rows / cols / ref / mag[nsamp] (mag: zeros for bf16) and ck_ref / ck_mag / ck_csum, each
+// [M / tile rows][N].  Nothing is launched on a refused argument (-2).
+int diag_gemm_verify(int dt, const void* A, const void* Bt, const void* C, const double* csum, int M, int N, int K,
+                     int geom, int nsamp, double ck_tol, double* max_err, double* ck_err, long long* ck_out,
+                     double* ck_floor, int* rows, int* cols, double* ref, double* mag, double* ck_ref,
+                     double* ck_mag, double* ck_csum) {
+  if ((dt != DT_BF16 && dt != DT_FP8) || (geom != 0 && geom != 1) || (dt == DT_FP8 && geom == 0)) {
+    g_err = "gemm_verify: dt 0 (bf16) or 1 (fp8), geom 0 (128^2 tiles, bf16 only) or 1 (256^2 tiles)";
+    return -2;
+  }
+  const int tile = geom ? V2_BM : BM, kmul = dt == DT_FP8 ? 128 : BK;
+  if (M <= 0 || N <= 0 || K <= 0 || M % tile || N % tile || K % kmul) {
+    g_err = "gemm_verify: M, N must be multiples of the tile (128 for geom 0, 256 for geom 1), K of 64 (bf16) or 128 "
+            "(fp8)";
+    return -2;
+  }
+  if (nsamp < 1) {
+    g_err = "gemm_verify: nsamp must be at least 1";
+    return -2;
+  }
+  if (!A || !Bt || !C || !max_err || (ck_tol >= 0.0 && (!ck_err || !ck_out))) {
+    g_err = "gemm_verify: null operand, output or result pointer";
+    return -2;
+  }
+  if (csum && geom == 0) {
+    g_err = "gemm_verify: fused column sums come with 256^2 tiles (geom 1) only";
+    return -2;
+  }
+  int device = 0;
+  HIP_CHECK(hipGetDevice(&device));
+  VerifyOut vo;
+  vo.rows = rows, vo.cols = cols, vo.ref = ref, vo.mag = mag;
+  vo.ck_ref = ck_ref, vo.ck_mag = ck_mag, vo.ck_csum = ck_csum;
+  const TileGeom g = geom ? kGeomV3 : kGeomV1;
+  return dt == DT_FP8 ? gemm_verify<GemmFp8>(device, A, Bt, C, csum, M, N, K, g, nsamp, ck_tol, max_err, ck_err,
+                                             ck_out, ck_floor, vo)
+                      : gemm_verify<GemmBf16>(device, A, Bt, C, csum, M, N, K, g, nsamp, ck_tol, max_err, ck_err,
+                                              ck_out, ck_floor, vo);
+}
+
+// The diagnostics' own operand fill (dt 0: fill_bf16_kernel, 1: fill_fp8_kernel) of `n` elements at device pointer
+// `ptr`, complete on return.
+int diag_gemm_fill(int dt, void* ptr, size_t n, unsigned long long seed) {
+  if ((dt != DT_BF16 && dt != DT_FP8) || !ptr || n == 0) {
+    g_err = "gemm_fill: dt 0 (bf16) or 1 (fp8), a buffer of at least one element";
+    return -2;
+  }
+  if (dt == DT_FP8) GemmFp8::fill(ptr, n, seed);
+  else GemmBf16::fill(ptr, n, seed);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  return 0;
 }
 
 // HBM streams over `bytes` per buffer: copy (read+write), read-only, write-only, in TB/s.  The bytes the rates are

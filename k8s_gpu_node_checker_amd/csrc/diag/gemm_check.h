@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../common/hip_host.h"
+#include "gemm_verdict.h"
 #include "types.h"
 
 namespace {
@@ -28,7 +29,8 @@ __global__ void gather_kernel(const T* C, const int* rows, const int* cols, floa
   if (i < nsamp) out[i] = static_cast<float>(C[static_cast<size_t>(rows[i]) * N + cols[i]]);
 }
 
-// Deterministic pseudo-random bf16 in [-1, 1).
+// Deterministic pseudo-random bf16 in [-1, 1]: the fp32 value lies in [-1, 1), and the hashes within 2^-9 of the
+// top round to bf16 1.0.
 __global__ void fill_bf16_kernel(__bf16* p, size_t n, uint64_t seed) {
   for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n;
        i += static_cast<size_t>(gridDim.x) * blockDim.x) {
@@ -50,13 +52,7 @@ __global__ void fill_fp8_kernel(uint8_t* p, size_t n, uint64_t seed) {
   }
 }
 
-__device__ __forceinline__ double e4m3_value(uint8_t b) {
-  const int e = (b >> 3) & 15, m = b & 7;
-  const double v = e == 0 ? m / 8.0 * 0.015625 : (1.0 + m / 8.0) * ldexp(1.0, e - 7);
-  return (b & 0x80) ? -v : v;
-}
-
-// fp64 reference of sampled fp8 outputs, plus sum |a*b| (the scale of the MX MFMA's accumulation error)
+// fp64 reference (operands decoded by gemm_verdict.h's e4m3_value) of sampled fp8 outputs, plus sum |a*b| (the scale of the MX MFMA's accumulation error)
 __global__ void gemm_ref_fp8_kernel(const uint8_t* A, const uint8_t* Bt, const int* rows, const int* cols,
                                     double* out, double* mag, int nsamp, int K) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

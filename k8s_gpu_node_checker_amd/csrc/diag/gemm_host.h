@@ -13,6 +13,7 @@
 #include "../common/hip_host.h"
 #include "gemm_check.h"
 #include "gemm_kernels.h"
+#include "gemm_verdict.h"
 
 namespace {
 
@@ -180,26 +181,21 @@ bool gemm_fused(int dt, int M, int N) {
   return v >= 4 || (v == 3 && v3_ck_path());
 }
 
-// Output tiles of a launch and the group_m of their blockIdx regrouping (tile_order.h, which also maps a tile back
-// to the XCD that computed it: tile_xcds).
-struct TileGeom {
-  int rows, cols, group_m;
-};
+// The tiles of the 128^2 kernel (v1) and of the 256^2 ones (TileGeom: gemm_verdict.h)
 constexpr TileGeom kGeomV1{BM, BN, 8}, kGeomV3{V2_BM, V2_BN, 4};
 
-// Whole-output check of C = A . Bt^T (the ck_* kernels).  ck_out[0] bad tiles, [1] bad columns, [2..9] bad tiles
-// per XCD, [10] / [11] the first bad tile's (row, column) in tiles or -1; *max_err the worst |csum - ref| / mag.
-// A NaN or infinite sum counts as bad.  *floor_out (optional) = tol * the largest mag of any column: an output wrong
-// by more than that (plus the healthy residual) is flagged whichever column it is in.
-constexpr int kCkOut = 12;
+// Whole-output check of C = A . Bt^T: the ck_* kernels form ref, mag and (fp32 C) the column sums, and
+// checksum_verdict (gemm_verdict.h, which documents *max_err, ck_out[kCkOut] and *floor_out) judges them on the host.
 // With `fused` (the OUT_BF16_CK kernel's csum[M / 128][N], device memory) the column sums come from the
-// kernel itself, its 128-row halves added per tile row in fp64, and C is not read.
+// kernel itself, its 128-row halves added per tile row in fp64, and C is not read.  out_ref / out_mag / out_csum
+// (optional, host, [M / g.rows][N] each) receive what was judged.
 template <int DT>
 int gemm_checksum(int device, const void* A, const void* Bt, const float* C, int M, int N, int K, TileGeom g,
                   double tol, double* max_err, long long* ck_out, const double* fused = nullptr,
-                  double* floor_out = nullptr) {
+                  double* floor_out = nullptr, double* out_ref = nullptr, double* out_mag = nullptr,
+                  double* out_csum = nullptr) {
   const int rb = g.rows;
-  const int nblk = M / rb, tiles_n = N / g.cols;
+  const int nblk = M / rb;
   const size_t kb = sizeof(double) * static_cast<size_t>(nblk) * K, nb = sizeof(double) * static_cast<size_t>(nblk) * N;
   DevBuf asum, aabs, ref, mag, csum;
   HIP_CHECK(asum.alloc(device, kb));
@@ -217,50 +213,14 @@ int gemm_checksum(int device, const void* A, const void* Bt, const float* C, int
                        static_cast<double*>(csum.ptr), N, rb);
   HIP_CHECK(hipGetLastError());
   const size_t cnt = static_cast<size_t>(nblk) * N;
-  std::vector<double> hr(cnt), hm(cnt), hc(cnt);
+  const int halves = fused ? rb / 128 : 1;
+  std::vector<double> hr(cnt), hm(cnt), hc(cnt * halves);
   HIP_CHECK(hipMemcpy(hr.data(), ref.ptr, nb, hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(hm.data(), mag.ptr, nb, hipMemcpyDeviceToHost));
-  if (fused) {
-    const int halves = rb / 128;
-    std::vector<double> h128(cnt * halves);
-    HIP_CHECK(hipMemcpy(h128.data(), fused, nb * halves, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt; ++i) {
-      const size_t tb = i / N, j = i % N;
-      double v = 0.0;
-      for (int h = 0; h < halves; ++h) v += h128[(tb * halves + h) * N + j];
-      hc[i] = v;
-    }
-  } else {
-    HIP_CHECK(hipMemcpy(hc.data(), csum.ptr, nb, hipMemcpyDeviceToHost));
-  }
-  const std::vector<int> xcd = tile_xcds(nblk, tiles_n, g.group_m);
-  std::vector<char> bad(static_cast<size_t>(nblk) * tiles_n, 0);
-  double worst = 0.0, max_mag = 0.0;
-  long long cols = 0;
-  for (size_t i = 0; i < cnt; ++i) {
-    max_mag = std::max(max_mag, hm[i]);
-    const double e = std::fabs(hc[i] - hr[i]) / std::max(hm[i], 1e-30);
-    if (!(e <= tol)) {  // also NaN
-      ++cols;
-      const size_t tb = i / N, j = i % N;
-      bad[tb * tiles_n + j / g.cols] = 1;
-    }
-    worst = std::isfinite(e) ? std::max(worst, e) : HUGE_VAL;
-  }
-  for (int i = 0; i < kCkOut; ++i) ck_out[i] = 0;
-  ck_out[1] = cols;
-  ck_out[10] = ck_out[11] = -1;
-  for (size_t t = 0; t < bad.size(); ++t) {
-    if (!bad[t]) continue;
-    ++ck_out[0];
-    if (xcd[t] >= 0) ++ck_out[2 + xcd[t]];
-    if (ck_out[10] < 0) {
-      ck_out[10] = static_cast<long long>(t / tiles_n);
-      ck_out[11] = static_cast<long long>(t % tiles_n);
-    }
-  }
-  *max_err = worst;
-  if (floor_out != nullptr) *floor_out = tol * max_mag;
+  HIP_CHECK(hipMemcpy(hc.data(), fused ? fused : csum.ptr, nb * halves, hipMemcpyDeviceToHost));
+  checksum_verdict(hr.data(), hm.data(), hc.data(), halves, nblk, N, g, tol, max_err, ck_out, floor_out, out_csum);
+  if (out_ref != nullptr) std::copy(hr.begin(), hr.end(), out_ref);
+  if (out_mag != nullptr) std::copy(hm.begin(), hm.end(), out_mag);
   return 0;
 }
 
@@ -294,27 +254,6 @@ hipError_t inject_output_ck(__bf16* C, double* csum, long long elem, int M, int 
   if ((e = hipMemcpy(&sum, cs, sizeof(sum), hipMemcpyDeviceToHost)) != hipSuccess) return e;
   sum += by_delta ? delta : static_cast<double>(static_cast<float>(v)) - static_cast<double>(static_cast<float>(old));
   return hipMemcpy(cs, &sum, sizeof(sum), hipMemcpyHostToDevice);
-}
-
-// |got - ref| beyond the rounding of a bf16 output (at most half an ulp: 2^-8 of |value|, with margin), so the
-// sampled checks of the bf16-output kernel keep the tolerances of the fp32 one
-// (a NaN stays NaN: std::max would turn it into 0)
-inline double beyond_bf16_rounding(double got, double ref) {
-  const double e = std::fabs(got - ref) - std::ldexp(std::max(std::fabs(got), std::fabs(ref)), -8) * 1.01;
-  return e > 0.0 || std::isnan(e) ? e : 0.0;
-}
-
-// The `nsamp` (row, column) pairs of an M x N output that a diagnostic run checks against its reference kernel
-void sample_indices(uint64_t seed, int nsamp, int M, int N, std::vector<int>& rows, std::vector<int>& cols) {
-  rows.resize(nsamp);
-  cols.resize(nsamp);
-  uint64_t x = seed;
-  for (int i = 0; i < nsamp; ++i) {
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    rows[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(M));
-    x = x * 6364136223846793005ULL + 1442695040888963407ULL;
-    cols[i] = static_cast<int>((x >> 33) % static_cast<uint64_t>(N));
-  }
 }
 
 }  // namespace

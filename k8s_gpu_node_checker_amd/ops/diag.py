@@ -318,6 +318,8 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
         "diag_gemm_bf16_launch": (launch, None), "diag_gemm_fp8_launch": (launch, None),
         "diag_gemm_fp4_launch": (launch, None),
         "diag_gemm_launch_ck": ([I, V, V, V, V, I, I, I, V], None), "diag_gemm_ck_path": ([I] * 3, I),
+        "diag_gemm_verify": ([I, V, V, V, V, I, I, I, I, I, D, pD, pD, pLL, pD, pI, pI] + [pD] * 5, None),
+        "diag_gemm_fill": ([I, V, Z, ctypes.c_ulonglong], None),
         "diag_gemm_bf16": (gemm, None), "diag_gemm_fp8": (gemm, None),
         "diag_hbm_bandwidth": ([I, Z, I, LL, I] + [pD] * 3 + [pU], None),
         "diag_memtest": ([I, Z, U64, I, LL, LL, I, I, pU, pU, pD], None),
@@ -510,6 +512,43 @@ def gemm_launch_ck(dtype: str, a_ptr: int, bt_ptr: int, c_ptr: int, csum_ptr: in
     if m % 256 or n % 256 or k % (128 if dt else 64):
         raise ValueError("gemm_ck: M, N must be multiples of 256 and K of 64 (bf16) or 128 (fp8)")
     _check(lib().diag_gemm_launch_ck(dt, a_ptr, bt_ptr, c_ptr, csum_ptr, m, n, k, stream))
+
+
+def gemm_verify(dtype: str, a_ptr: int, bt_ptr: int, c_ptr: int, csum_ptr: Optional[int], m: int, n: int, k: int,
+                geom: int, samples: int = 4096, ck_tol: float = -1.0) -> Dict[str, Any]:
+    """The ``gemm`` / ``gemm_fp8`` diagnostics' referee on caller-owned device memory (a raw-pointer test entry
+    point): the sampled check and, with ``ck_tol`` >= 0, the tile checksums of ``C`` against ``A @ Bt.T``.
+    ``csum_ptr`` None: ``C`` is fp32; else ``C`` is bf16 and ``csum_ptr`` the fused ``csum[m // 128][n]``.  ``geom``
+    0 = 128x128 tiles in groups of 8 (bf16 only), 1 = 256x256 in groups of 4.  Returns the diagnostics' four outputs
+    (``max_err``, ``ck_err``, ``ck_out``, ``ck_floor``; the last three 0 without checksums) and what was judged:
+    ``rows`` / ``cols`` / ``ref`` / ``mag`` per sample and, with checksums, ``ck_ref`` / ``ck_mag`` / ``ck_csum`` as
+    lists of ``m // tile rows`` x ``n`` doubles in row-major order."""
+    dt = {"bf16": 0, "fp8": 1}[dtype]
+    ns = max(int(samples), 0)
+    err, ck, floor = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    out = (ctypes.c_longlong * 12)()
+    rows, cols = (ctypes.c_int * ns)(), (ctypes.c_int * ns)()
+    ref, mag = (ctypes.c_double * ns)(), (ctypes.c_double * ns)()
+    tile = 256 if geom else 128
+    cnt = (m // tile) * n if ck_tol >= 0 and m > 0 and n > 0 else 0
+    ck_arrays = [(ctypes.c_double * cnt)() for _ in range(3)]
+    as_pd = lambda arr: ctypes.cast(arr, ctypes.POINTER(ctypes.c_double))  # noqa: E731
+    _check(lib().diag_gemm_verify(dt, a_ptr, bt_ptr, c_ptr, csum_ptr, m, n, k, geom, int(samples), float(ck_tol),
+                                  ctypes.byref(err), ctypes.byref(ck), out, ctypes.byref(floor),
+                                  ctypes.cast(rows, ctypes.POINTER(ctypes.c_int)),
+                                  ctypes.cast(cols, ctypes.POINTER(ctypes.c_int)), as_pd(ref), as_pd(mag),
+                                  *[as_pd(a) if cnt else None for a in ck_arrays]))
+    res = {"max_err": err.value, "ck_err": ck.value, "ck_out": list(out), "ck_floor": floor.value,
+           "rows": list(rows), "cols": list(cols), "ref": list(ref), "mag": list(mag)}
+    for name, arr in zip(("ck_ref", "ck_mag", "ck_csum"), ck_arrays):
+        res[name] = list(arr)
+    return res
+
+
+def gemm_fill(dtype: str, ptr: int, n: int, seed: int) -> None:
+    """The diagnostics' own operand fill of ``n`` elements (bf16, or E4M3 bytes) at device pointer ``ptr`` (a
+    raw-pointer test entry point); complete on return."""
+    _check(lib().diag_gemm_fill({"bf16": 0, "fp8": 1}[dtype], ptr, n, seed))
 
 
 def _ref(test: str, key: Any, scale: float) -> float:

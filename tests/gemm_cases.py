@@ -1,7 +1,8 @@
 """Helpers for the GEMM kernel tests (no tests here): guard-banded buffers, the product of the public GEMM knobs,
 and operands whose product is exact in fp32 whatever the accumulation order.
 
-Used by test_gemm_exact_inputs_cpu.py (which proves the helpers on the CPU) and test_gpu_gemm_matrix.py.
+Used by test_gemm_exact_inputs_cpu.py (which proves the helpers on the CPU), test_gpu_gemm_matrix.py and
+test_gpu_gemm_referee.py (the operands and the fp64 model of the diagnostics' referee, at the end of the file).
 """
 import itertools
 import math
@@ -192,3 +193,54 @@ def row_bytes(dtype, k):
     b = k * ELEM_BYTES[dtype]
     assert b == math.floor(b)
     return int(b)
+
+
+# --- the referee's operands and its fp64 model ----------------------------------------------------------------------
+
+# E4M3 codes of the integers 0..8 (1.0 = 0x38: exponent field 7; 3 = 1.5 * 2, 5 = 1.25 * 4, 7 = 1.75 * 4)
+FP8_INT_CODES = (0x00, 0x38, 0x40, 0x44, 0x48, 0x4A, 0x4C, 0x4E, 0x50)
+# the 254 finite E4M3 codes: every byte but the two NaNs
+FP8_FINITE = [c for c in range(256) if c & 0x7F != 0x7F]
+
+
+def integer_operand(dtype, rows, k, gen):
+    """``rows x k`` independent integers in -8..8, exact in bf16 and in E4M3: ``(operand in dtype, values as
+    float64)``.  The fp8 bytes come from the code table above, not from a cast."""
+    v = torch.randint(-8, 9, (rows, k), generator=gen, dtype=torch.int64)
+    if dtype == "fp8":
+        bits = torch.tensor(FP8_INT_CODES, dtype=torch.int64)[v.abs()] | ((v < 0).to(torch.int64) << 7)
+        return bits.to(torch.uint8).view(torch.float8_e4m3fn), v.to(torch.float64)
+    return v.to(torch.bfloat16), v.to(torch.float64)
+
+
+def wide_bf16_operand(rows, k, gen):
+    """Normal deviates scaled by 2^-20 .. 2^20 element by element, so a row spans about 40 binades: ``(bf16,
+    its values as float64)``."""
+    x = torch.randn(rows, k, generator=gen, dtype=torch.float64)
+    e = torch.randint(-20, 21, (rows, k), generator=gen, dtype=torch.int64)
+    t = torch.ldexp(x, e).to(torch.float32).to(torch.bfloat16)
+    return t, t.to(torch.float64)
+
+
+def wide_fp8_operand(rows, k, gen):
+    """Every finite E4M3 code, cycled along each row in a random order of the row's own: ``(float8_e4m3fn, values as
+    float64 decoded from the bits)``."""
+    order = torch.rand(rows, len(FP8_FINITE), generator=gen).argsort(dim=1)
+    codes = torch.tensor(FP8_FINITE, dtype=torch.int64)[order][:, torch.arange(k) % len(FP8_FINITE)]
+    bits = codes.to(torch.uint8)
+    return bits.view(torch.float8_e4m3fn), decode_e4m3(bits)
+
+
+def referee_model(a64, bt64, tile_rows):
+    """What the diagnostics' referee must compute for ``C = a64 @ bt64.T``, in float64: the product ``c``, each
+    output's ``mag`` = sum |a b|, and for every ``tile_rows``-high block of rows tb and column j the checksum
+    reference ``ck_ref`` = sum_k (sum_i a[i][k]) bt[j][k] and its magnitude ``ck_mag`` with absolute values."""
+    return {"c": a64 @ bt64.T, "mag": a64.abs() @ bt64.abs().T,
+            "ck_ref": block_sums(a64, tile_rows) @ bt64.T,
+            "ck_mag": block_sums(a64.abs(), tile_rows) @ bt64.abs().T}
+
+
+def gamma(n, u):
+    """Higham's gamma_n(u) = n u / (1 - n u): the relative error bound of n roundings of unit roundoff u."""
+    assert n * u < 1
+    return n * u / (1 - n * u)

@@ -463,7 +463,7 @@ NOT_FAKED = frozenset(
     [f"diag_{op}_gemm_{k}" for op in ("set", "get")
      for k in ("variant", "epilogue", "tail", "buffer_loads", "schedule", "fp8_unscaled")]
     + ["diag_gemm_bf16_launch", "diag_gemm_fp8_launch", "diag_gemm_fp4_launch", "diag_gemm_launch_ck",
-       "diag_gemm_ck_path", "diag_poll_selftest"])
+       "diag_gemm_verify", "diag_gemm_fill", "diag_gemm_ck_path", "diag_poll_selftest"])
 
 
 def test_fake_abi_has_every_entry_point_the_front_end_calls_with_the_c_arity():

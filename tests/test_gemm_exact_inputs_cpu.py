@@ -124,3 +124,58 @@ def test_knob_matrix_is_the_full_product():
         assert len({(c["epilogue"], c["buffer_loads"], c["schedule"], c["fp8_unscaled"]) for c in v3}) == 8 * forms
         assert {c["variant"] for c in cfgs} - {"v3"} == others
         assert all(set(c) == {"variant", "epilogue", "buffer_loads", "schedule", "fp8_unscaled", "tail"} for c in cfgs)
+
+
+# --- the referee's operands and model (test_gpu_gemm_referee.py) ----------------------------------------------------
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp8"])
+def test_integer_operands_are_the_integers_they_claim(dtype):
+    gen = torch.Generator().manual_seed(5)
+    t, v = G.integer_operand(dtype, 64, 192, gen)
+    assert set(v.unique().tolist()) == {float(i) for i in range(-8, 9)}
+    if dtype == "fp8":
+        assert torch.equal(G.decode_e4m3(t.view(torch.uint8)), v)  # the code table, by the format
+    assert torch.equal(t.to(torch.float64), v)  # ... and by the cast
+    # a product of K = 1024 such operands is exact in fp32 and its checksums in fp64
+    assert 64 * 1024 < 2 ** 24 and 256 * 8 * 8 * 1024 < 2 ** 53
+
+
+def test_wide_fp8_rows_hold_every_finite_code_and_their_products_stay_exact_in_fp64():
+    gen = torch.Generator().manual_seed(6)
+    t, v = G.wide_fp8_operand(16, 384, gen)
+    bits = t.view(torch.uint8).to(torch.int64)
+    assert len(G.FP8_FINITE) == 254 and bool(torch.isfinite(v).all())
+    assert torch.equal(t.to(torch.float64), v)
+    for r in range(16):
+        assert sorted(bits[r, :254].tolist()) == G.FP8_FINITE and torch.equal(bits[r, 254:], bits[r, :130])
+    assert not torch.equal(bits[0], bits[1])
+    t128, _ = G.wide_fp8_operand(4, 128, gen)
+    assert all(len(set(t128.view(torch.uint8)[r].tolist())) == 128 for r in range(4))
+    # values are multiples of 2^-9 up to 448, so every product and partial sum is a multiple of 2^-18.  A row holds
+    # each code at most ceil(K / 254) times, so by the rearrangement inequality sum_k |a_k b_k| of two such rows is
+    # at most ceil(K / 254) * sum_c v_c^2; over 256 rows and K = 1024 that stays below 2^53 units of 2^-18: exact.
+    nz = v[v != 0].abs()
+    assert float(nz.min()) == 2.0 ** -9 and float(nz.max()) == 448.0
+    squares = float((G.decode_e4m3(torch.tensor(G.FP8_FINITE)) ** 2).sum())
+    assert 256 * -(-1024 // 254) * squares / 2.0 ** -18 < 2.0 ** 53
+
+
+def test_wide_bf16_rows_span_about_forty_binades():
+    gen = torch.Generator().manual_seed(7)
+    t, v = G.wide_bf16_operand(8, 1024, gen)
+    assert t.dtype == torch.bfloat16 and torch.equal(t.to(torch.float64), v) and bool(torch.isfinite(v).all())
+    span = torch.log2(v.abs().clamp_min(1e-300))
+    for r in range(8):
+        assert 36 <= float(span[r].max() - span[r][v[r] != 0].min()) <= 60
+
+
+def test_referee_model_on_a_problem_small_enough_to_write_out():
+    a = torch.tensor([[1.0, -2.0], [3.0, 4.0], [-5.0, 6.0], [7.0, 8.0]], dtype=torch.float64)
+    bt = torch.tensor([[1.0, 1.0], [2.0, -1.0], [0.0, -3.0]], dtype=torch.float64)
+    m = G.referee_model(a, bt, 2)
+    assert m["c"].tolist() == [[-1.0, 4.0, 6.0], [7.0, 2.0, -12.0], [1.0, -16.0, -18.0], [15.0, 6.0, -24.0]]
+    assert m["mag"].tolist() == [[3.0, 4.0, 6.0], [7.0, 10.0, 12.0], [11.0, 16.0, 18.0], [15.0, 22.0, 24.0]]
+    assert m["ck_ref"].tolist() == [[6.0, 6.0, -6.0], [16.0, -10.0, -42.0]]  # the column sums of c per 2-row block
+    assert m["ck_mag"].tolist() == [[10.0, 14.0, 18.0], [26.0, 38.0, 42.0]]
+    assert torch.equal(m["ck_ref"], G.block_sums(m["c"], 2))
+    assert G.gamma(1024, 2.0 ** -24) == 1024 * 2.0 ** -24 / (1 - 1024 * 2.0 ** -24)

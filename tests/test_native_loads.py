@@ -95,7 +95,8 @@ DIAG_EXPORTS = frozenset((
     "diag_get_gemm_variant", "diag_get_gemm_epilogue", "diag_get_gemm_tail", "diag_get_gemm_buffer_loads",
     "diag_get_gemm_schedule", "diag_get_gemm_fp8_unscaled",
     "diag_gemm_bf16_launch", "diag_gemm_fp8_launch", "diag_gemm_fp4_launch", "diag_gemm_launch_ck", "diag_gemm_ck_path",
-    "diag_gemm_bf16", "diag_gemm_fp8", "diag_hbm_bandwidth", "diag_memtest", "diag_mfma_burn_slots", "diag_mfma_burn",
+    "diag_gemm_verify", "diag_gemm_fill", "diag_gemm_bf16", "diag_gemm_fp8", "diag_hbm_bandwidth", "diag_memtest",
+    "diag_mfma_burn_slots", "diag_mfma_burn",
     "diag_lds_test", "diag_regfile_slots", "diag_regfile_test", "diag_valu_burn", "diag_l2_bandwidth", "diag_hbm_xcd",
     "diag_host_link", "diag_poll_selftest", "diag_p2p_copy", "diag_p2p_fan"))
 
@@ -112,7 +113,7 @@ def test_diag_exports_match_their_ctypes_signatures(monkeypatch):
     L = diag.lib()
     assert isinstance(L, ctypes.CDLL)
     exports = diag_c_exports()
-    assert len(DIAG_EXPORTS) == 36 and set(exports) == DIAG_EXPORTS, sorted(set(exports) ^ DIAG_EXPORTS)
+    assert len(DIAG_EXPORTS) == 38 and set(exports) == DIAG_EXPORTS, sorted(set(exports) ^ DIAG_EXPORTS)
     for name, params in exports.items():
         fn = getattr(L, name)  # AttributeError: not exported
         if not params:
