@@ -446,8 +446,10 @@ class Agent:
                  diag_setup: Optional[tuple] = None, diag_xgmi_kernel: bool = False,
                  diag_atomics: bool = False, diag_lanes: bool = False,
                  diag_scalar: bool = False, diag_matrix: bool = False, diag_vmem: bool = False,
-                 diag_cvt: bool = False):
+                 diag_cvt: bool = False, diag_hbmscan: bool = False):
         self.node = node
+        # every device's suite also runs the hbmscan diagnostic (ops/hbmscan.py): it holds the GPU's free memory
+        self.diag_hbmscan = diag_hbmscan
         self.diag_vmem = diag_vmem  # every device's suite also runs the vmem diagnostic (ops/vmem.py)
         self.diag_cvt = diag_cvt  # every device's suite also runs the cvt diagnostic (ops/cvt.py)
         self.diag_matrix = diag_matrix  # every device's suite also runs the matrix diagnostic (ops/matrix.py)
@@ -901,7 +903,8 @@ class Agent:
         kw["deadline"] = time.monotonic() + 0.9 * self.diag_timeout
         extra = tuple(t for t, on in (("atomics", self.diag_atomics), ("lanes", self.diag_lanes),
                                          ("scalar", self.diag_scalar), ("matrix", self.diag_matrix),
-                                         ("vmem", self.diag_vmem), ("cvt", self.diag_cvt)) if on)
+                                         ("vmem", self.diag_vmem), ("cvt", self.diag_cvt),
+                                         ("hbmscan", self.diag_hbmscan)) if on)
         if extra:
             kw["extra"] = extra
         job = self.workers.device(self.diag_level, d, kw, self._diag_done, host)
@@ -1203,6 +1206,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="every GPU's diagnostics also run the cvt test: every format conversion of the vector ALU "
                          "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
                          "wrong words located to their SIMD")
+    ap.add_argument("--diag-hbmscan", action="store_true",
+                    help="every GPU's diagnostics also run the hbmscan test: every free byte of the GPU's memory but a "
+                         "2 GiB reserve through four phases, every 16-byte word checked, wrong words named (stuck bit, "
+                         "alias, region, scattered); it holds the GPU's free memory while it runs and stops by itself "
+                         "at half of what --diag-timeout leaves it (reported incomplete, not failed)")
     ap.add_argument("--diag-isolation", choices=ISOLATION, default="process",
                     help="process (default): each cycle's HIP diagnostics run in disposable child processes, so the "
                          "agent never initialises HIP, a hung one is SIGKILLed at --diag-timeout and a GPU fault "
@@ -1272,7 +1280,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                   isolation=args.diag_isolation, diag_xgmi_kernel=args.diag_xgmi_kernel,
                   diag_atomics=args.diag_atomics, diag_lanes=args.diag_lanes,
                   diag_scalar=args.diag_scalar, diag_matrix=args.diag_matrix, diag_vmem=args.diag_vmem,
-                  diag_cvt=args.diag_cvt)
+                  diag_cvt=args.diag_cvt, diag_hbmscan=args.diag_hbmscan)
     if args.diag_baseline_reset and agent.baselines is not None:
         spec = args.diag_baseline_reset.strip()
         gone = agent.baselines.drop(None if spec.lower() == "all" else spec.split(","))

@@ -163,6 +163,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "vmem": "36loads+23stores-chains4+8bounds+l1+4ldsdma-r1",
     # no rate verdict either (ops/cvt.py): the op groups a clean result covered (the ops themselves: cvt.OPS)
     "cvt": "classic+bf16+fp8+scalef32-chains4-r1",
+    # no rate verdict either (ops/hbmscan.py): the phases and steps a clean result covered
+    "hbmscan": "addr3+invert16+random4+fade3-flat16-r1",
 }
 
 
@@ -935,6 +937,14 @@ def cvt_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return cvt.cvt_test(device, **kw)
 
 
+def hbmscan_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in hbmscan diagnostic (``ops/hbmscan.hbmscan_test``, its own library): every free byte of the device's
+    memory but a reserve, in chunks, through four phases with every 16-byte word checked, and a named finding
+    (stuck bit, alias, region, scattered).  No level runs it; ``run(extra=("hbmscan",))`` does."""
+    from . import hbmscan  # lazily: only who asks for the test needs libmi355x_hbmscan.so
+    return hbmscan.hbmscan_test(device, **kw)
+
+
 def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in lanes diagnostic (``ops/lanes.lanes_test``, its own library): every lane-crossing instruction of a
     wave (DPP, the permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane / readfirstlane) in chains that
@@ -1258,17 +1268,21 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "matrix": ("matrix_test", {}),  # in no level: run(extra=("matrix",))
     "vmem": ("vmem_test", {}),  # in no level: run(extra=("vmem",))
     "cvt": ("cvt_test", {}),  # in no level: run(extra=("cvt",))
+    "hbmscan": ("hbmscan_test", {}),  # in no level: run(extra=("hbmscan",))
 }
 # error counts only: nothing to scale
 _UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test", "cvt_test"))
+                       "vmem_test", "cvt_test", "hbmscan_test"))
+# share of what is left of run()'s deadline that the hbmscan may use (as P2P_SHARE for the xGMI matrix): it stops by
+# itself there and reports ``complete`` false, instead of being killed by the agent's watchdog with nothing to show
+HBMSCAN_SHARE = 0.5
 
 
-def _one(test: str, device: int, scale: Scale) -> Dict[str, Any]:
+def _one(test: str, device: int, scale: Scale, more: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     if test not in _TESTS:
         raise ValueError(f"unknown diagnostic {test!r}")
     fn, kwargs = _TESTS[test]
-    return globals()[fn](device, **kwargs, **({} if fn in _UNSCALED else {"scale": scale}))
+    return globals()[fn](device, **{**kwargs, **(more or {})}, **({} if fn in _UNSCALED else {"scale": scale}))
 
 
 def _slow_only(res: Dict[str, Any]) -> bool:
@@ -1322,10 +1336,12 @@ def use_host_lock(lock: Any, cell: Any, label: Optional[int] = None) -> None:
 
 def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         memory_partition: Optional[str] = None, power_fraction: Optional[float] = None,
-        deadline: Optional[float] = None, extra: Sequence[str] = ()) -> Dict[str, Dict[str, Any]]:
+        deadline: Optional[float] = None, extra: Sequence[str] = (),
+        options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``),
-    each treated as the level's own are.
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``),
+    each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
+    (``{"hbmscan": {"gib": 64}}``).  With a ``deadline`` the hbmscan gets ``HBMSCAN_SHARE`` of what is left of it.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
     lands below the degraded line is measured once more and the better of the two is reported.  Tests of
@@ -1349,12 +1365,15 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
             if why is not None:  # not this GPU's finding: the report says whose turn it still is
                 out[name] = {"pass": True, "skipped": why, "detail": ""}
                 continue
+        more = dict((options or {}).get(name) or {})
+        if name == "hbmscan" and deadline is not None and "deadline_s" not in more:
+            more["deadline_s"] = max(1.0, HBMSCAN_SHARE * (deadline - time.monotonic()))
         try:
-            res = _one(test, device, scale)
+            res = _one(test, device, scale, more) if more else _one(test, device, scale)
             for _ in range(REMEASURE):
                 if not _slow_only(res):
                     break
-                again = _one(test, device, scale)
+                again = _one(test, device, scale, more) if more else _one(test, device, scale)
                 again["retried"] = True
                 if _goodness(again) > _goodness(res):
                     res = again
@@ -1416,6 +1435,12 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
                 f"XCDs, round {mode.get('round', '?')} denorm {mode.get('denorm', '?')}, {r.get('errors', 0)} wrong words; "
                 f"{r.get('ms', 0):.1f} ms, mean {rate:.0f} G conversions/s")
+    if test == "hbmscan":
+        from .hbmscan import finding_text
+        state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
+        return (f"{r.get('tested_gib', 0):.4g} of {r.get('total_gib', 0):.4g} GiB ({r.get('coverage', 0):.1%}) in "
+                f"{r.get('chunks', '?')} chunks{state}, {r.get('errors', 0)} wrong words, finding "
+                f"{finding_text(r.get('finding') or {'kind': 'none'})}; {r.get('wall_s', 0):.1f} s")
     if test == "scalar":
         p = r.get("parts") or {}
         salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
@@ -1490,12 +1515,14 @@ def render_text(out: Dict[str, Any]) -> str:
     return "\n".join(lines) + "\n"
 
 
-def run_devices(level: int, devices: List[int], parallel: int = 8,
-                extra: Sequence[str] = ()) -> Dict[int, Dict[str, Dict[str, Any]]]:
+def run_devices(level: int, devices: List[int], parallel: int = 8, extra: Sequence[str] = (),
+                options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[int, Dict[str, Dict[str, Any]]]:
     """:func:`run` on every device, at most ``parallel`` at once (one host thread per GPU, as the node agent
     runs them; host-resource tests still take turns under their lock).  A device whose run raised reports it
-    as a failed ``run`` test instead of losing the other devices' results.  ``extra``: as :func:`run`'s."""
-    more = {"extra": tuple(extra)} if extra else {}  # none: the call run() has always got
+    as a failed ``run`` test instead of losing the other devices' results.  ``extra``, ``options``: as :func:`run`'s."""
+    more: Dict[str, Any] = {"extra": tuple(extra)} if extra else {}  # none: the call run() has always got
+    if options:
+        more["options"] = options
     out: Dict[int, Dict[str, Dict[str, Any]]] = {}
     missing: List[NativeUnavailable] = []  # no library at all: raised in the caller's thread, not per device
 
@@ -1559,7 +1586,8 @@ def fabric_tests(devices: List[int], p2p: bool = True, rccl: bool = True,
 
 
 def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
-            clock: Any = None, progress: Any = None, extra: Sequence[str] = ()) -> Dict[str, Any]:
+            clock: Any = None, progress: Any = None, extra: Sequence[str] = (),
+            options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Any]:
     """Acceptance burn-in: the per-device suite of ``level`` on every device, round after round, for
     ``minutes``.  Passes only if every round of every device passed; reports each rate per device as
     min / median / max over the rounds (a GPU that drifts or throttles under sustained load shows as a wide
@@ -1577,7 +1605,8 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
     from ..models.peers import judge_node
     node_rounds: Dict[str, int] = {}  # rounds with a node-wide shortfall, per test.metric
     while True:
-        res = run_devices(level, devices, parallel, **({"extra": tuple(extra)} if extra else {}))
+        res = run_devices(level, devices, parallel, **({"extra": tuple(extra)} if extra else {}),
+                          **({"options": options} if options else {}))
         for f in judge_node(res):  # each round's GPUs against each other, as the agent judges them
             key = f"{f['test']}.{f['metric']}"
             node_rounds[key] = node_rounds.get(key, 0) + 1
@@ -1616,7 +1645,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1655,6 +1684,12 @@ def main(argv=None) -> int:
                     help="also run the cvt diagnostic on every device: every format conversion of the vector ALU "
                          "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
                          "wrong words located to their SIMD (ops/cvt.py)")
+    ap.add_argument("--hbmscan", action="store_true",
+                    help="also run the hbmscan diagnostic on every device: every free byte of its memory but a 2 GiB "
+                         "reserve through four phases, every 16-byte word checked, and a named finding (stuck bit, "
+                         "alias, region, scattered); holds the GPU's free memory while it runs (ops/hbmscan.py)")
+    ap.add_argument("--hbmscan-gib", type=float, default=None, metavar="N",
+                    help="with --hbmscan: test N GiB instead of all free memory (under 2 GiB the caches may answer)")
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="level 2: bound the node-level tests (s); a hung xGMI pair or collective is reported failed")
     ap.add_argument("--duration", type=float, default=0.0,
@@ -1669,9 +1704,12 @@ def main(argv=None) -> int:
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
     opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
-                                             ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt))
+                                             ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt),
+                                             ("hbmscan", args.hbmscan))
                    if on)
-    more = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
+    more: Dict[str, Any] = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
+    if args.hbmscan and args.hbmscan_gib is not None:
+        more["options"] = {"hbmscan": {"gib": args.hbmscan_gib}}
     if args.duration > 0:
         import sys as _sys
         b = burn_in(args.level, devices, args.duration, max(1, args.parallel),

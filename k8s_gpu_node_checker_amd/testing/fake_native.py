@@ -1,6 +1,6 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
-``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so`` and
-``libmi355x_fabric.so``.
+``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so``,
+``libmi355x_hbmscan.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -577,6 +577,112 @@ class FakeAtomicsLib:
             ms[k] = self.ms if on else 0.0
             for x in range(8):
                 xcd_waves[8 * k + x] = max(1, -(-words // 64) * adders // self.xcds) if on and x < self.xcds else 0
+        return 0
+
+
+def hbmscan_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeHbmscanLib` stands in for, read from csrc/hbmscan/hbmscan.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "hbmscan", "hbmscan.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(hbmscan_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeHbmscanLib:
+    """``libmi355x_hbmscan.so`` for a node of ``n`` GPUs of 288 GiB with ``free_gib`` free: every word clean.
+
+    bad:        ``{device: wrong words}``, all bit 37 read as 1 where 0 was written, the first at +0x1a2b3c40 of
+                chunk 5 in the ``invert`` phase: finding ``stuck_bit``
+    incomplete: the devices whose scan runs out of its deadline after ``random`` step 1 (whatever ``deadline_s`` is)
+    physical:   the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``hbmscan{device}`` in ``calls`` (empty = never called), their deadlines in ``deadlines``."""
+
+    TOTAL = 309220868096  # hipMemGetInfo's total on an MI355X
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[int, int]] = None, incomplete: Tuple[int, ...] = (),
+                 free_gib: float = 287.0, gbs: float = 5000.0, physical: Optional[int] = None):
+        self.n, self.bad, self.incomplete = n, dict(bad or {}), set(incomplete)
+        self.free, self.gbs, self.physical = int(free_gib * (1 << 30)), gbs, physical
+        self.calls: List[str] = []
+        self.deadlines: List[float] = []
+        self.err = b"boom"
+
+    def hbmscan_last_error(self) -> bytes:
+        return self.err
+
+    def hbmscan_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def hbmscan_plan(self, free_bytes, total_bytes, reserve, limit, chunk, plan_out):
+        target = max(0, free_bytes - reserve)
+        target = min(target, limit) if limit else target
+        target -= target % 16
+        count = -(-target // chunk) if chunk >= 16 and chunk % 16 == 0 else 0
+        if free_bytes > total_bytes or target < 16 or not 1 <= count <= 4096:
+            self.err = b"hbmscan plan: need free <= total, a target of at least 16 bytes and at most 4096 chunks"
+            return -2
+        for i in range(count):
+            plan_out[i] = chunk if i + 1 < count else target - i * chunk
+        return count
+
+    def hbmscan_want(self, phase, step, global_word, seed, out):
+        if not 0 <= phase < 4 or not 0 <= step < (3, 16, 256, 3)[phase]:
+            self.err = b"hbmscan want: no such phase or step"
+            return -2
+        out[0] = out[1] = out[2] = out[3] = 0  # (the fake models no content: tests/test_hbmscan_cpu.py has the model)
+        return 0
+
+    def hbmscan_classify(self, records, n, hist, index_base, tested_words, finding_out):
+        f = finding_out._obj if hasattr(finding_out, "_obj") else finding_out
+        f.kind, f.bit, f.direction, f.chunk = (1, 37, 1, -1) if n else (0, -1, -1, -1)
+        return 0
+
+    def hbmscan_test(self, device, limit, reserve, chunk, min_chunk, hold_ms, random_passes, seed, deadline_s,
+                     index_base, flips, n_flips, stuck_word, stuck_bit, stuck_value, alias_a, alias_b, fail_alloc_at,
+                     totals, phase_errors, phase_ms, phase_wall_ms, phase_bytes, records, hist, finding):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"hbmscan{device}")
+        self.deadlines.append(float(deadline_s))
+        plan = (ctypes.c_ulonglong * 4096)()
+        count = self.hbmscan_plan(self.free, self.TOTAL, reserve, limit, chunk, plan) if 0 <= device < self.n else -2
+        if count < 0 or not 1 <= random_passes <= 64 or not 0 <= hold_ms <= 60000 or deadline_s < 0:
+            self.err = (b"hbmscan test: need a valid device, chunk and min_chunk multiples of 16 (chunk up to 16 GiB), "
+                        b"hold_ms 0..60000, random_passes 1..64, deadline_s >= 0")
+            return -2
+        tested = sum(plan[i] for i in range(count))
+        bad = self.bad.get(device, 0)
+        stopped = device in self.incomplete
+        for i, v in enumerate((self.TOTAL, self.free, tested, tested, count, bad, min(bad, 64), 0 if stopped else 1,
+                               1 if tested < 2 << 30 else 0, 2 if stopped else 3, 1 if stopped else 2, 0, 0, 0, 0, 0)):
+            totals[i] = v
+        sweeps = (4, 24, 6 * random_passes, 4)
+        for ph in range(4):
+            ran = ph < 2 or not stopped
+            phase_errors[ph] = bad if ph == 1 else 0
+            phase_bytes[ph] = float(tested * sweeps[ph]) if ran else 0.0
+            phase_ms[ph] = phase_bytes[ph] / (self.gbs * 1e9) * 1e3
+            phase_wall_ms[ph] = phase_ms[ph] + (2 * hold_ms if ph == 3 and ran else 0)
+        for i in range(256):
+            hist[i] = 0
+        hist[2 * 37 + 1] = min(bad, 4096)
+        for i in range(min(bad, 64)):
+            r = records[i]
+            r.phase, r.step, r.chunk, r.word = 1, 1, 5 if count > 5 else 0, (0x1a2b3c40 >> 4) + i
+            r.global_word = r.chunk * (chunk // 16) + r.word
+            for lane in range(4):
+                r.want[lane], r.got[lane] = 0, (1 << 5) if lane == 1 else 0
+        f = finding._obj if hasattr(finding, "_obj") else finding
+        f.kind, f.bit, f.direction, f.chunk, f.victim, f.source, f.span = (1, 37, 1, -1, 0, 0, 0) if bad else (0, -1, -1, -1, 0, 0, 0)
         return 0
 
 
@@ -1420,9 +1526,9 @@ class NarrowedDiagLib:
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
-            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, **diag_kw) -> None:
+            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1458,3 +1564,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import cvt as cvt_mod
     clib = FakeCvtLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(cvt or {}))
     cvt_mod.lib = lambda: clib
+    from ..ops import hbmscan as hbmscan_mod
+    hlib = FakeHbmscanLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(hbmscan or {}))
+    hbmscan_mod.lib = lambda: hlib
