@@ -165,6 +165,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "cvt": "classic+bf16+fp8+scalef32-chains4-r1",
     # no rate verdict either (ops/hbmscan.py): the phases and steps a clean result covered
     "hbmscan": "addr3+invert16+random4+fade3-flat16-r1",
+    # no rate verdict either (ops/ifetch.py): the walk's blocks and steps per block, and the branch ops a clean result covered
+    "ifetch": "walk1024x16-paths64+branch10-chains4-r1",
 }
 
 
@@ -937,6 +939,15 @@ def cvt_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return cvt.cvt_test(device, **kw)
 
 
+def ifetch_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in ifetch diagnostic (``ops/ifetch.ifetch_test``, its own library): the front end of every CU -- a
+    data-dependent walk over a code footprint larger than the instruction cache, every constant a literal of the
+    instruction stream, and every branch instruction in scalar chains -- checked bit for bit against the host's
+    model.  No level runs it; ``run(extra=("ifetch",))`` does."""
+    from . import ifetch  # lazily: only who asks for the test needs libmi355x_ifetch.so
+    return ifetch.ifetch_test(device, **kw)
+
+
 def hbmscan_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in hbmscan diagnostic (``ops/hbmscan.hbmscan_test``, its own library): every free byte of the device's
     memory but a reserve, in chunks, through four phases with every 16-byte word checked, and a named finding
@@ -1269,10 +1280,11 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "vmem": ("vmem_test", {}),  # in no level: run(extra=("vmem",))
     "cvt": ("cvt_test", {}),  # in no level: run(extra=("cvt",))
     "hbmscan": ("hbmscan_test", {}),  # in no level: run(extra=("hbmscan",))
+    "ifetch": ("ifetch_test", {}),  # in no level: run(extra=("ifetch",))
 }
 # error counts only: nothing to scale
 _UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test", "cvt_test", "hbmscan_test"))
+                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test"))
 # share of what is left of run()'s deadline that the hbmscan may use (as P2P_SHARE for the xGMI matrix): it stops by
 # itself there and reports ``complete`` false, instead of being killed by the agent's watchdog with nothing to show
 HBMSCAN_SHARE = 0.5
@@ -1339,7 +1351,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = (),
         options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``),
     each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
     (``{"hbmscan": {"gib": 64}}``).  With a ``deadline`` the hbmscan gets ``HBMSCAN_SHARE`` of what is left of it.
 
@@ -1435,6 +1447,16 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
                 f"XCDs, round {mode.get('round', '?')} denorm {mode.get('denorm', '?')}, {r.get('errors', 0)} wrong words; "
                 f"{r.get('ms', 0):.1f} ms, mean {rate:.0f} G conversions/s")
+    if test == "ifetch":
+        p = r.get("parts") or {}
+        walk, br = p.get("walk") or {}, p.get("branch") or {}
+        rows = walk.get("rows") or {}
+        feet = [v.get("footprint_bytes", 0) for v in rows.values()]
+        span = f"{min(feet) / 1024:.0f}-{max(feet) / 1024:.0f} KiB of code" if feet else "no rows"
+        per = "/".join(f"{v.get('ns_per_block', 0):.0f}" for v in rows.values())
+        return (f"walk {len(rows)} footprints ({span}) x {walk.get('steps', '?')} blocks per wave ({per} ns per block), "
+                f"{len(br.get('ops') or {})} branch ops x {br.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of "
+                f"{r.get('xcds', '?')} XCDs, {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
     if test == "hbmscan":
         from .hbmscan import finding_text
         state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
@@ -1645,7 +1667,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1684,6 +1706,10 @@ def main(argv=None) -> int:
                     help="also run the cvt diagnostic on every device: every format conversion of the vector ALU "
                          "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
                          "wrong words located to their SIMD (ops/cvt.py)")
+    ap.add_argument("--ifetch", action="store_true",
+                    help="also run the ifetch diagnostic on every device: a data-dependent walk over more code than the "
+                         "instruction cache holds and every branch instruction, checked bit for bit against the host's "
+                         "model, wrong words located to the SIMD that executed (ops/ifetch.py)")
     ap.add_argument("--hbmscan", action="store_true",
                     help="also run the hbmscan diagnostic on every device: every free byte of its memory but a 2 GiB "
                          "reserve through four phases, every 16-byte word checked, and a named finding (stuck bit, "
@@ -1705,7 +1731,7 @@ def main(argv=None) -> int:
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
     opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
                                              ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt),
-                                             ("hbmscan", args.hbmscan))
+                                             ("hbmscan", args.hbmscan), ("ifetch", args.ifetch))
                    if on)
     more: Dict[str, Any] = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.hbmscan and args.hbmscan_gib is not None:

@@ -1,6 +1,6 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
 ``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so``,
-``libmi355x_hbmscan.so`` and ``libmi355x_fabric.so``.
+``libmi355x_hbmscan.so``, ``libmi355x_ifetch.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -892,6 +892,158 @@ class FakeCvtLib:
         return -1
 
 
+def ifetch_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeIfetchLib` stands in for, read from csrc/ifetch/ifetch.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "ifetch", "ifetch.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(ifetch_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeIfetchLib:
+    """``libmi355x_ifetch.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row of both parts clean on every
+    SIMD, the walk kernel's blocks ``BLOCK_BYTES`` apart.
+
+    bad:      ``{(device, part, row): wrong words}`` with part ``"walk"`` (row: an nb) or ``"branch"`` (row: an op
+              index), all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the first of them lane 9 (the walk) /
+              chain 1 (a branch op), read as ``want ^ 0x100``
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    Calls are logged as ``ifetch_walk{device}`` / ``ifetch_branch{device}`` in ``calls``: empty = never called."""
+
+    OPS = 10
+    NB = 1024
+    SLOTS = 4096
+    BLOCK_BYTES = 456
+    WANT = 0x1FE7C4ED
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, str, int], int]] = None,
+                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 physical: Optional[int] = None):
+        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
+        self.physical = physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def ifetch_last_error(self) -> bytes:
+        return self.err
+
+    def ifetch_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def ifetch_slots(self) -> int:
+        return self.SLOTS
+
+    def ifetch_blocks(self) -> int:
+        return self.NB
+
+    def ifetch_block_map(self, device, addrs):
+        for b in range(self.NB):
+            addrs[b] = 0x7f0000100000 + self.BLOCK_BYTES * (self.NB - 1 - b)
+        return 0
+
+    def _device(self, device):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return None
+            return self.physical
+        return device
+
+    def _fill_map(self, simd_map, grid, launches, ticks):
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = ticks * launches
+
+    def _record(self, first, k, wrong, where):
+        first[4 * k] = where if wrong else (1 << 64) - 1
+        first[4 * k + 1] = 0
+        first[4 * k + 2] = self.WANT ^ 0x100 if wrong else 0
+        first[4 * k + 3] = self.WANT if wrong else 0
+
+    def ifetch_walk_test(self, device, blocks, steps, reps, nbs, nrows, seed, inject_row, inject_block, inject_skip_step,
+                         errors, first, ms, footprint, visited, simd_map, blocks_run):
+        device = self._device(device)
+        if device is None:
+            return -1
+        self.calls.append(f"ifetch_walk{device}")
+        rows = [nbs[i] for i in range(nrows)] if 1 <= nrows <= 64 else []
+        if not 0 <= device < self.n or blocks < 0 or not 1 <= steps <= 1 << 16 or reps < 1 or not rows \
+                or not all(1 <= v <= self.NB for v in rows):
+            self.err = (b"ifetch walk: need a valid device, blocks >= 0 (0: 4 per CU), steps 1..2^16, reps >= 1 and 1..64 "
+                        b"rows of nb 1..1024")
+            return -2
+        grid = blocks or self.xcds * 32 * 4
+        _put(blocks_run, ctypes.c_int, grid)
+        if inject_row >= 0 and (inject_row >= nrows or not 0 <= inject_block < grid or inject_skip_step >= steps):
+            self.err = (b"ifetch walk: inject_row must be one of the rows, inject_block inside the grid and "
+                        b"inject_skip_step below steps")
+            return -2
+        for nb in rows:  # 64 paths x steps draws: the stand-in refuses what cannot cover nb blocks on average
+            if 64 * steps < 4 * nb:
+                self.err = b"ifetch walk: the 64 paths of seed %d visit fewer than %d blocks in %d steps" % (seed, nb, steps)
+                return -2
+        self._fill_map(simd_map, grid, (reps + 1) * len(rows), 1000 * steps)
+        for k, nb in enumerate(rows):
+            wrong = self.bad.get((device, "walk", nb), 0) + (1 if k == inject_row else 0)
+            errors[k] = wrong
+            self._record(first, k, wrong, (self.bad_row << 16) | (9 << 8))
+            ms[k] = self.ms
+            footprint[k] = self.BLOCK_BYTES * nb
+            visited[k] = nb
+            if wrong:
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+        return 0
+
+    def ifetch_branch_test(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
+                           errors, first, ms, simd_map, blocks_run):
+        device = self._device(device)
+        if device is None:
+            return -1
+        self.calls.append(f"ifetch_branch{device}")
+        chosen = [ops[i] for i in range(nops)] if 1 <= nops <= self.OPS else []
+        if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not chosen \
+                or not all(0 <= k < self.OPS for k in chosen):
+            self.err = (b"ifetch branch: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a "
+                        b"list of known ops")
+            return -2
+        grid = blocks or self.xcds * 32 * 4
+        _put(blocks_run, ctypes.c_int, grid)
+        if inject_op >= 0 and (inject_op not in chosen or not 0 <= inject_block < grid or inject_skip_iter >= iters):
+            self.err = (b"ifetch branch: inject_op must be in the list, inject_block inside the grid and inject_skip_iter "
+                        b"below iters")
+            return -2
+        self._fill_map(simd_map, grid, (reps + 1) * len(chosen), 100 * iters)
+        for k in range(self.OPS):
+            on = k in chosen
+            wrong = (self.bad.get((device, "branch", k), 0) + (1 if k == inject_op else 0)) if on else 0
+            errors[k] = wrong
+            self._record(first, k, wrong, (self.bad_row << 16) | 1)
+            ms[k] = self.ms if on else 0.0
+            if wrong:
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+        return 0
+
+    def ifetch_apply_blocks(self, device, blocks, n, x, p, x_out, p_out):
+        self.err = b"ifetch apply_blocks: the stand-in has no wave to run a block on"
+        return -1
+
+    def ifetch_apply(self, device, op, n, w, cond, out):
+        self.err = b"ifetch apply: the stand-in has no wave to apply an instruction on"
+        return -1
+
+
 def matrix_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1526,9 +1678,9 @@ class NarrowedDiagLib:
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
-            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, **diag_kw) -> None:
+            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, ifetch: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1567,3 +1719,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import hbmscan as hbmscan_mod
     hlib = FakeHbmscanLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(hbmscan or {}))
     hbmscan_mod.lib = lambda: hlib
+    from ..ops import ifetch as ifetch_mod
+    ilib = FakeIfetchLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(ifetch or {}))
+    ifetch_mod.lib = lambda: ilib
