@@ -167,6 +167,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "hbmscan": "addr3+invert16+random4+fade3-flat16-r1",
     # no rate verdict either (ops/ifetch.py): the walk's blocks and steps per block, and the branch ops a clean result covered
     "ifetch": "walk1024x16-paths64+branch10-chains4-r1",
+    # no rate verdict either (ops/handoff.py): the forms and placements a clean result covered, and the slab handed off
+    "handoff": "fence+wt+wt_add+granule-cross+same-slab4k-r1",
 }
 
 
@@ -948,6 +950,15 @@ def ifetch_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return ifetch.ifetch_test(device, **kw)
 
 
+def handoff_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in handoff diagnostic (``ops/handoff.handoff_test``, its own library): a ring of ping-pong hand-offs
+    between workgroups inside one launch, across XCDs and inside one -- the L2 write-back, the L1 invalidate,
+    write-through stores, L1-bypassing loads, agent-scope flags and atomic adds -- every word checked bit for bit, a
+    wrong one classified stale or corrupt, every spin bounded.  No level runs it; ``run(extra=("handoff",))`` does."""
+    from . import handoff  # lazily: only who asks for the test needs libmi355x_handoff.so
+    return handoff.handoff_test(device, **kw)
+
+
 def hbmscan_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in hbmscan diagnostic (``ops/hbmscan.hbmscan_test``, its own library): every free byte of the device's
     memory but a reserve, in chunks, through four phases with every 16-byte word checked, and a named finding
@@ -1281,10 +1292,11 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "cvt": ("cvt_test", {}),  # in no level: run(extra=("cvt",))
     "hbmscan": ("hbmscan_test", {}),  # in no level: run(extra=("hbmscan",))
     "ifetch": ("ifetch_test", {}),  # in no level: run(extra=("ifetch",))
+    "handoff": ("handoff_test", {}),  # in no level: run(extra=("handoff",))
 }
 # error counts only: nothing to scale
 _UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test"))
+                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test", "handoff_test"))
 # share of what is left of run()'s deadline that the hbmscan may use (as P2P_SHARE for the xGMI matrix): it stops by
 # itself there and reports ``complete`` false, instead of being killed by the agent's watchdog with nothing to show
 HBMSCAN_SHARE = 0.5
@@ -1351,7 +1363,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = (),
         options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``, ``"handoff"``),
     each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
     (``{"hbmscan": {"gib": 64}}``).  With a ``deadline`` the hbmscan gets ``HBMSCAN_SHARE`` of what is left of it.
 
@@ -1457,6 +1469,14 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         return (f"walk {len(rows)} footprints ({span}) x {walk.get('steps', '?')} blocks per wave ({per} ns per block), "
                 f"{len(br.get('ops') or {})} branch ops x {br.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of "
                 f"{r.get('xcds', '?')} XCDs, {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
+    if test == "handoff":
+        rows = r.get("rows") or {}
+        per = "/".join(f"{v.get('us_per_round', 0):.1f}" for v in rows.values())
+        waits = sum(v.get("timeouts", 0) for v in rows.values())
+        state = "" if r.get("complete", True) else f", incomplete ({waits} waits ran out: re-run on an idle device)"
+        return (f"{len(rows)} rows x {r.get('rounds', '?')} rounds on {r.get('blocks', '?')} workgroups, {r.get('simds', '?')} "
+                f"SIMDs of {r.get('xcds', '?')} XCDs ({per} us per round), {r.get('errors', 0)} wrong words{state}; "
+                f"{r.get('ms', 0):.1f} ms")
     if test == "hbmscan":
         from .hbmscan import finding_text
         state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
@@ -1667,7 +1687,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--handoff] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1710,6 +1730,11 @@ def main(argv=None) -> int:
                     help="also run the ifetch diagnostic on every device: a data-dependent walk over more code than the "
                          "instruction cache holds and every branch instruction, checked bit for bit against the host's "
                          "model, wrong words located to the SIMD that executed (ops/ifetch.py)")
+    ap.add_argument("--handoff", action="store_true",
+                    help="also run the handoff diagnostic on every device: a ring of hand-offs between workgroups inside "
+                         "one launch, across XCDs and inside one, in four forms (release / acquire fences, write-through "
+                         "stores, an atomic counter, tagged granules), every word checked bit for bit, a wrong one "
+                         "classified stale or corrupt, every spin bounded (ops/handoff.py)")
     ap.add_argument("--hbmscan", action="store_true",
                     help="also run the hbmscan diagnostic on every device: every free byte of its memory but a 2 GiB "
                          "reserve through four phases, every 16-byte word checked, and a named finding (stuck bit, "
@@ -1731,7 +1756,8 @@ def main(argv=None) -> int:
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
     opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
                                              ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt),
-                                             ("hbmscan", args.hbmscan), ("ifetch", args.ifetch))
+                                             ("hbmscan", args.hbmscan), ("ifetch", args.ifetch),
+                                             ("handoff", args.handoff))
                    if on)
     more: Dict[str, Any] = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.hbmscan and args.hbmscan_gib is not None:

@@ -1,6 +1,6 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
 ``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so``,
-``libmi355x_hbmscan.so``, ``libmi355x_ifetch.so`` and ``libmi355x_fabric.so``.
+``libmi355x_hbmscan.so``, ``libmi355x_ifetch.so``, ``libmi355x_handoff.so`` and ``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -1044,6 +1044,158 @@ class FakeIfetchLib:
         return -1
 
 
+def handoff_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeHandoffLib` stands in for, read from csrc/handoff/handoff.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "handoff", "handoff.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(handoff_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeHandoffLib:
+    """``libmi355x_handoff.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row clean and complete, block b on
+    CU ``b // xcds`` of XCD ``b % xcds`` (so ``cross`` pairs lie on different XCDs and ``same`` pairs on one).
+
+    bad:      ``{(device, row): wrong words}`` (row: the native index, form * 2 + placement), all on SIMD map row
+              ``bad_row`` (xcd5/se1/cu7/simd2), the first of them lane 9, word 37 of block 3's slab in round 5 of the
+              first timed launch, read as that word of round 4 (``stale``: ``STALE``) or, for a row listed in
+              ``corrupt``, as ``want ^ 0x100``
+    timeout:  ``{(device, row): waits}`` that ran out, the first workgroup 2's for the flag of block 3 in round 5
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    The hooks act as the library's do: the flip gives 1 ``corrupt`` word at ``inject_block``, the stale word 1 ``stale``
+    word at its consumer, the mute 1 timeout of its consumer and no launch completes that round.
+    Calls are logged as ``handoff{device}`` in ``calls``: empty = never called."""
+
+    ROWS = 8
+    SLOTS = 4096
+    LDS = 81 * 1024
+    WANT = 0x4A2D0FF1
+    STALE = 0x0DD0FF1C
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None, corrupt: Tuple[int, ...] = (),
+                 timeout: Optional[Dict[Tuple[int, int], int]] = None,
+                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.4,
+                 physical: Optional[int] = None):
+        self.n, self.bad, self.corrupt, self.timeout = n, dict(bad or {}), set(corrupt), dict(timeout or {})
+        self.bad_row, self.xcds, self.ms, self.physical = bad_row, xcds, ms, physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def handoff_last_error(self) -> bytes:
+        return self.err
+
+    def handoff_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def handoff_slots(self) -> int:
+        return self.SLOTS
+
+    def handoff_lds_bytes(self) -> int:
+        return self.LDS
+
+    def _slot(self, block: int) -> int:
+        cu = block // self.xcds
+        return ((block % self.xcds) << 7) | ((cu // 8) << 5) | (cu % 8)
+
+    def handoff_test(self, device, blocks, rounds, reps, rows, nrows, seed, spin_ms, jitter, inject_row, inject_block,
+                     inject_round, inject_stale_word, inject_mute, errors, words, timeouts, first, tmo, pairs, ms,
+                     simd_map, blocks_run):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"handoff{device}")
+        chosen = [rows[i] for i in range(nrows)] if 1 <= nrows <= self.ROWS else []
+        if not 0 <= device < self.n or not 1 <= rounds <= 1 << 15 or reps < 1 or not 1 <= spin_ms <= 1000 or not chosen \
+                or not all(0 <= k < self.ROWS for k in chosen):
+            self.err = b"handoff: need a valid device, rounds 1..2^15, reps >= 1, spin_ms 1..1000 and a list of known rows"
+            return -2
+        cus = self.xcds * 32
+        grid = blocks or cus
+        if grid < 16 or grid > cus or grid % 8:
+            self.err = (b"handoff: blocks must be 0 (one per CU) or a multiple of 8 from 16 to the CU count %d, not %d: "
+                        b"a larger grid is not co-resident, a smaller one pairs a workgroup with itself" % (cus, grid))
+            return -2
+        _put(blocks_run, ctypes.c_int, grid)
+        if inject_row >= 0 and inject_row not in chosen:
+            self.err = b"handoff: inject_row must be in the list"
+            return -2
+        if inject_row >= 0:
+            limit = 512 if inject_row // 2 == 3 else 1024
+            if not 0 <= inject_block < grid or not 0 <= inject_round < rounds or inject_stale_word >= limit \
+                    or (inject_stale_word >= 0 and (inject_round < 1 or inject_mute)):
+                self.err = (b"handoff: inject_block must lie inside the grid, inject_round inside the rounds, "
+                            b"inject_stale_word inside the slab and in a round >= 1 (round 0 has no round before), and "
+                            b"one hook at a time")
+                return -2
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        launches = (reps + 1) * len(chosen)
+        for b in range(grid):
+            for simd in range(4):
+                simd_map[3 * ((self._slot(b) << 2) | simd)] = launches
+                simd_map[3 * ((self._slot(b) << 2) | simd) + 2] = 1000 * rounds * launches
+        for k in range(self.ROWS):
+            on = k in chosen
+            stride, per = (8 if k % 2 else 1), (512 if k // 2 == 3 else 1024)
+            errors[k] = timeouts[k] = 0
+            words[k] = grid * rounds * per * (reps + 1) if on else 0
+            for j in range(8):
+                first[8 * k + j] = 0
+            first[8 * k] = (1 << 64) - 1
+            for j in range(4):
+                tmo[4 * k + j] = 0
+            same = sum(1 for b in range(grid) if self._slot(b) >> 7 == self._slot((b + stride) % grid) >> 7)
+            pairs[3 * k], pairs[3 * k + 1], pairs[3 * k + 2] = (grid - same, same, 0) if on else (0, 0, 0)
+            ms[k] = self.ms if on else 0.0
+            if not on:
+                continue
+            record = None  # where, producer, round, word, got, want, class, age, launch
+            wrong = self.bad.get((device, k), 0)
+            if wrong:
+                cls = 2 if k in self.corrupt else 1
+                record = ((self.bad_row << 16) | 9, 3, 5, 37, self.WANT ^ 0x100 if cls == 2 else self.STALE, self.WANT,
+                          cls, 0 if cls == 2 else 1, 1)
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+            waits = self.timeout.get((device, k), 0)
+            gave_up = (2, 1, 3, 5) if waits else None
+            if k == inject_row:
+                consumer = (inject_block - stride) % grid
+                if inject_mute:
+                    waits += 1
+                    gave_up = (consumer, 4 - 1 if k // 2 == 3 else 1, inject_block, inject_round)
+                    words[k] -= grid * (rounds - inject_round) * per  # nobody finishes that round
+                else:
+                    at = consumer if inject_stale_word >= 0 else inject_block
+                    row = (self._slot(at) << 2) | 0
+                    producer = inject_block if inject_stale_word >= 0 else (inject_block + stride) % grid
+                    record = ((row << 16) | (inject_stale_word // 4 % 64 if inject_stale_word >= 0 else 0), producer,
+                              inject_round, max(inject_stale_word, 0),
+                              self.STALE if inject_stale_word >= 0 else self.WANT ^ 0x10, self.WANT,
+                              1 if inject_stale_word >= 0 else 2, 1 if inject_stale_word >= 0 else 0, 0)
+                    wrong += 1
+                    simd_map[3 * row + 1] += 1
+            errors[k] = wrong
+            if record:
+                where, producer, rnd, word, got, want, cls, age, launch = record
+                for j, v in enumerate((where, (producer << 32) | (rnd << 16) | word, got, want, self._slot(producer), cls,
+                                       age, launch)):
+                    first[8 * k + j] = v
+            timeouts[k] = waits
+            if gave_up:
+                for j, v in enumerate(gave_up):
+                    tmo[4 * k + j] = v
+        return 0
+
+
 def matrix_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1678,9 +1830,10 @@ class NarrowedDiagLib:
 
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
-            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, ifetch: Optional[Dict] = None, **diag_kw) -> None:
+            vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, ifetch: Optional[Dict] = None,
+            handoff: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``; ``ops.handoff``: ``FakeHandoffLib(n, **handoff)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1722,3 +1875,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import ifetch as ifetch_mod
     ilib = FakeIfetchLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(ifetch or {}))
     ifetch_mod.lib = lambda: ilib
+    from ..ops import handoff as handoff_mod
+    holib = FakeHandoffLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(handoff or {}))
+    handoff_mod.lib = lambda: holib
