@@ -447,8 +447,9 @@ class Agent:
                  diag_atomics: bool = False, diag_lanes: bool = False,
                  diag_scalar: bool = False, diag_matrix: bool = False, diag_vmem: bool = False,
                  diag_cvt: bool = False, diag_hbmscan: bool = False, diag_ifetch: bool = False,
-                 diag_handoff: bool = False):
+                 diag_handoff: bool = False, diag_scratch: bool = False):
         self.node = node
+        self.diag_scratch = diag_scratch  # every device's suite also runs the scratch diagnostic (ops/scratch.py)
         self.diag_handoff = diag_handoff  # every device's suite also runs the handoff diagnostic (ops/handoff.py)
         self.diag_ifetch = diag_ifetch  # every device's suite also runs the ifetch diagnostic (ops/ifetch.py)
         # every device's suite also runs the hbmscan diagnostic (ops/hbmscan.py): it holds the GPU's free memory
@@ -908,7 +909,7 @@ class Agent:
                                          ("scalar", self.diag_scalar), ("matrix", self.diag_matrix),
                                          ("vmem", self.diag_vmem), ("cvt", self.diag_cvt),
                                          ("hbmscan", self.diag_hbmscan), ("ifetch", self.diag_ifetch),
-                                         ("handoff", self.diag_handoff)) if on)
+                                         ("handoff", self.diag_handoff), ("scratch", self.diag_scratch)) if on)
         if extra:
             kw["extra"] = extra
         job = self.workers.device(self.diag_level, d, kw, self._diag_done, host)
@@ -1218,6 +1219,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="every GPU's diagnostics also run the handoff test: hand-offs between workgroups inside one "
                          "launch, across XCDs and inside one, in four forms, every word checked bit for bit, a wrong one "
                          "classified stale or corrupt; every spin is bounded and a wait that ran out is reported, not failed")
+    ap.add_argument("--diag-scratch", action="store_true",
+                    help="every GPU's diagnostics also run the scratch test: private memory -- twice the device's wave "
+                         "slots of 1 KiB-per-lane frames written, held and read back, a wrong word classified alias, "
+                         "stale or corrupt, and the compiler's own locals and call frames")
     ap.add_argument("--diag-hbmscan", action="store_true",
                     help="every GPU's diagnostics also run the hbmscan test: every free byte of the GPU's memory but a "
                          "2 GiB reserve through four phases, every 16-byte word checked, wrong words named (stuck bit, "
@@ -1293,7 +1298,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                   diag_atomics=args.diag_atomics, diag_lanes=args.diag_lanes,
                   diag_scalar=args.diag_scalar, diag_matrix=args.diag_matrix, diag_vmem=args.diag_vmem,
                   diag_cvt=args.diag_cvt, diag_hbmscan=args.diag_hbmscan, diag_ifetch=args.diag_ifetch,
-                  diag_handoff=args.diag_handoff)
+                  diag_handoff=args.diag_handoff, diag_scratch=args.diag_scratch)
     if args.diag_baseline_reset and agent.baselines is not None:
         spec = args.diag_baseline_reset.strip()
         gone = agent.baselines.drop(None if spec.lower() == "all" else spec.split(","))

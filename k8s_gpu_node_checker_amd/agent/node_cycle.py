@@ -22,7 +22,8 @@ from typing import Any, Dict, List, Optional
 def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: int = 8,
         fabric: bool = True, xgmi_kernel: bool = False, atomics: bool = False, lanes: bool = False,
         scalar: bool = False, matrix: bool = False, vmem: bool = False, cvt: bool = False,
-        hbmscan: bool = False, ifetch: bool = False, handoff: bool = False) -> Dict[str, Any]:
+        hbmscan: bool = False, ifetch: bool = False, handoff: bool = False,
+        scratch: bool = False) -> Dict[str, Any]:
     """The cycle; returns the summary (never raises for a failed test: failures are in the result)."""
     from ..ops import diag
     from .agent import Agent
@@ -49,7 +50,7 @@ def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: 
                    **({"diag_scalar": True} if scalar else {}), **({"diag_matrix": True} if matrix else {}),
                    **({"diag_vmem": True} if vmem else {}), **({"diag_cvt": True} if cvt else {}),
                    **({"diag_hbmscan": True} if hbmscan else {}), **({"diag_ifetch": True} if ifetch else {}),
-                   **({"diag_handoff": True} if handoff else {}))
+                   **({"diag_handoff": True} if handoff else {}), **({"diag_scratch": True} if scratch else {}))
         rep = ag.probe_once()
     finally:
         diag.run = real_run  # type: ignore[assignment]
@@ -109,10 +110,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                     help="also run the ifetch diagnostic on every device (ops/ifetch.py)")
     ap.add_argument("--handoff", action="store_true",
                     help="also run the handoff diagnostic on every device (ops/handoff.py)")
+    ap.add_argument("--scratch", action="store_true",
+                    help="also run the scratch diagnostic on every device (ops/scratch.py)")
     args = ap.parse_args(argv)
     devices = [int(x) for x in args.devices.split(",") if x.strip()]
     res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel, args.atomics, args.lanes,
-              args.scalar, args.matrix, args.vmem, args.cvt, args.hbmscan, args.ifetch, args.handoff)
+              args.scalar, args.matrix, args.vmem, args.cvt, args.hbmscan, args.ifetch, args.handoff, args.scratch)
     print(json.dumps(res, separators=(",", ":"), default=str), flush=True)
     return 0
 

@@ -1,6 +1,6 @@
 """Build every native component in-tree (``k8s_gpu_node_checker_amd/_native/``).
 
-``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff] [--force]``
+``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff,scratch] [--force]``
 
 =====================  ==================================================  ==========================
 artefact               source                                              toolchain
@@ -19,11 +19,12 @@ artefact               source                                              toolc
 ``libmi355x_hbmscan.so`` ``csrc/hbmscan/hbmscan.hip`` (hbmscan diagnostic)      hipcc --offload-arch=gfx950
 ``libmi355x_ifetch.so`` ``csrc/ifetch/ifetch.hip`` (ifetch diagnostic)        hipcc --offload-arch=gfx950
 ``libmi355x_handoff.so`` ``csrc/handoff/handoff.hip`` (handoff diagnostic)     hipcc --offload-arch=gfx950
+``libmi355x_scratch.so`` ``csrc/scratch/scratch.hip`` (scratch diagnostic)     hipcc --offload-arch=gfx950
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
-The twelve HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
-lanes, scalar, matrix, vmem, cvt, ifetch and handoff also share ``csrc/common/simd_report.h``.
+The thirteen HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
+lanes, scalar, matrix, vmem, cvt, ifetch, handoff and scratch also share ``csrc/common/simd_report.h``.
 Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
 The ifetch library's one large kernel (more than 400 KiB of code) takes about 40 s to compile, the longest of all.
 
@@ -61,8 +62,8 @@ def _targets() -> Dict[str, Dict[str, object]]:
            f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"]
     # every HIP library is built by the same line (fabric adds RCCL after its sources); includes are relative, no -I
     hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
-    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all twelve share
-    simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the seven SIMD-located diagnostics
+    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all thirteen share
+    simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the eight SIMD-located diagnostics
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -167,6 +168,13 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "cmd": hip_cmd,
             "requires": hipcc,
         },
+        "scratch": {
+            "sources": [os.path.join(CSRC, "scratch", "scratch.hip")],
+            "headers": [os.path.join(CSRC, "scratch", "scratch_ref.h"), hip_host, simd_report],
+            "out": os.path.join(OUT, "libmi355x_scratch.so"),
+            "cmd": hip_cmd,
+            "requires": hipcc,
+        },
         "fabric": {
             "sources": [os.path.join(CSRC, "fabric", "fabric.hip")],
             "headers": [hip_host],
@@ -237,7 +245,7 @@ def build(only: Optional[Sequence[str]] = None, force: bool = False, verbose: bo
 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff,fabric")
+    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff,scratch,fabric")
     ap.add_argument("--force", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)

@@ -169,6 +169,8 @@ KERNEL_REVISION: Dict[str, str] = {
     "ifetch": "walk1024x16-paths64+branch10-chains4-r1",
     # no rate verdict either (ops/handoff.py): the forms and placements a clean result covered, and the slab handed off
     "handoff": "fence+wt+wt_add+granule-cross+same-slab4k-r1",
+    # no rate verdict either (ops/scratch.py): the isolate frame and grid, and the frames routines a clean result covered
+    "scratch": "isolate1k-x2slots+frames-index+calls-r1",
 }
 
 
@@ -959,6 +961,14 @@ def handoff_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     return handoff.handoff_test(device, **kw)
 
 
+def scratch_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+    """The opt-in scratch diagnostic (``ops/scratch.scratch_test``, its own library): private memory -- twice the device's wave slots of 1 KiB frames written, held and read
+    back with a wrong word classified alias, stale or corrupt, and the compiler's own locals and call frames.  No level
+    runs it; ``run(extra=("scratch",))`` does."""
+    from . import scratch  # lazily: only who asks for the test needs libmi355x_scratch.so
+    return scratch.scratch_test(device, **kw)
+
+
 def hbmscan_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
     """The opt-in hbmscan diagnostic (``ops/hbmscan.hbmscan_test``, its own library): every free byte of the device's
     memory but a reserve, in chunks, through four phases with every 16-byte word checked, and a named finding
@@ -1293,10 +1303,11 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "hbmscan": ("hbmscan_test", {}),  # in no level: run(extra=("hbmscan",))
     "ifetch": ("ifetch_test", {}),  # in no level: run(extra=("ifetch",))
     "handoff": ("handoff_test", {}),  # in no level: run(extra=("handoff",))
+    "scratch": ("scratch_test", {}),  # in no level: run(extra=("scratch",))
 }
 # error counts only: nothing to scale
 _UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test", "handoff_test"))
+                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test", "handoff_test", "scratch_test"))
 # share of what is left of run()'s deadline that the hbmscan may use (as P2P_SHARE for the xGMI matrix): it stops by
 # itself there and reports ``complete`` false, instead of being killed by the agent's watchdog with nothing to show
 HBMSCAN_SHARE = 0.5
@@ -1363,7 +1374,7 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = (),
         options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``, ``"handoff"``),
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``, ``"handoff"``, ``"scratch"``),
     each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
     (``{"hbmscan": {"gib": 64}}``).  With a ``deadline`` the hbmscan gets ``HBMSCAN_SHARE`` of what is left of it.
 
@@ -1477,6 +1488,11 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         return (f"{len(rows)} rows x {r.get('rounds', '?')} rounds on {r.get('blocks', '?')} workgroups, {r.get('simds', '?')} "
                 f"SIMDs of {r.get('xcds', '?')} XCDs ({per} us per round), {r.get('errors', 0)} wrong words{state}; "
                 f"{r.get('ms', 0):.1f} ms")
+    if test == "scratch":
+        rows = r.get("rows") or {}
+        return (f"{len(rows)} rows ({', '.join(rows)}) on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
+                f"{r.get('isolate_waves', '?')} isolate waves x {r.get('rounds', '?')} rounds ({r.get('co_resident_waves', '?')} "
+                f"frames live at once), {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
     if test == "hbmscan":
         from .hbmscan import finding_text
         state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
@@ -1687,7 +1703,7 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--handoff] [--format json|text]``:
+    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--handoff] [--scratch] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
     text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
     import argparse
@@ -1735,6 +1751,11 @@ def main(argv=None) -> int:
                          "one launch, across XCDs and inside one, in four forms (release / acquire fences, write-through "
                          "stores, an atomic counter, tagged granules), every word checked bit for bit, a wrong one "
                          "classified stale or corrupt, every spin bounded (ops/handoff.py)")
+    ap.add_argument("--scratch", action="store_true",
+                    help="also run the scratch diagnostic on every device: private memory -- twice the device's "
+                         "wave slots of 1 KiB-per-lane frames written, held and read back, a wrong word classified alias, "
+                         "stale or corrupt; the compiler's own locals and call frames, compared bit for bit with the "
+                         "host's run (ops/scratch.py)")
     ap.add_argument("--hbmscan", action="store_true",
                     help="also run the hbmscan diagnostic on every device: every free byte of its memory but a 2 GiB "
                          "reserve through four phases, every 16-byte word checked, and a named finding (stuck bit, "
@@ -1757,7 +1778,7 @@ def main(argv=None) -> int:
     opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
                                              ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt),
                                              ("hbmscan", args.hbmscan), ("ifetch", args.ifetch),
-                                             ("handoff", args.handoff))
+                                             ("handoff", args.handoff), ("scratch", args.scratch))
                    if on)
     more: Dict[str, Any] = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.hbmscan and args.hbmscan_gib is not None:

@@ -1,6 +1,7 @@
 """CPU stand-ins for the C ABIs of ``libmi355x_diag.so``, ``libmi355x_xgmi.so``, ``libmi355x_atomics.so``,
 ``libmi355x_lanes.so``, ``libmi355x_scalar.so``, ``libmi355x_matrix.so``, ``libmi355x_vmem.so``, ``libmi355x_cvt.so``,
-``libmi355x_hbmscan.so``, ``libmi355x_ifetch.so``, ``libmi355x_handoff.so`` and ``libmi355x_fabric.so``.
+``libmi355x_hbmscan.so``, ``libmi355x_ifetch.so``, ``libmi355x_handoff.so``, ``libmi355x_scratch.so`` and
+``libmi355x_fabric.so``.
 
 They implement the same calls with the same out-parameter protocol (values written through ctypes
 pointers), so ``ops/diag.py``, ``ops/xgmi.py`` and ``ops/fabric.py`` run unchanged on CPU with scripted results: a node of
@@ -1196,6 +1197,158 @@ class FakeHandoffLib:
         return 0
 
 
+def scratch_c_exports() -> Dict[str, List[str]]:
+    """The C ABI that :class:`FakeScratchLib` stands in for, read from csrc/scratch/scratch.hip the way
+    :func:`xgmi_c_exports` reads xgmi.hip."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "scratch", "scratch.hip")) as f:
+        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    out: Dict[str, List[str]] = {}
+    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
+        for name, params in re.findall(r"^\w[\w ]*[ *]+(scratch_\w+)\(([^)]*)\)\s*\{", block, re.M):
+            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+    return out
+
+
+class FakeScratchLib:
+    """``libmi355x_scratch.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row clean, wave w on SIMD ``w % 4``
+    of CU ``(w // 4) // xcds % 32`` of XCD ``(w // 4) % xcds``.
+
+    bad:      ``{(device, row): wrong words}`` (row: the native index, the position in ``ops.scratch.ROWS``), all on
+              SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the first of them lane 9 of wave 3 in the first timed
+              launch; on the isolate row it is classified as listed in ``classes`` (``{row: "alias" | "stale" |
+              "corrupt"}``, default ``corrupt``; an alias is written by wave 4)
+    physical: the node's ordinal of the one GPU a narrowed process sees as device 0 (``HIP_VISIBLE_DEVICES``)
+    The hooks act as the library's do: exactly one wrong word of the hook's class in the warm-up launch.
+    Calls are logged as ``scratch{device}`` in ``calls``: empty = never called."""
+
+    SLOTS = 4096
+    WANT = 0x5C7A7C11
+    FRAME = {"isolate": 1040, "index": 272, "calls": 400}
+
+    def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
+                 classes: Optional[Dict[int, str]] = None, bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2,
+                 xcds: int = 8, ms: float = 0.05, physical: Optional[int] = None):
+        from ..ops import scratch as ops_scratch
+        self.rows = len(ops_scratch.ROWS)
+        self.iso, self.index, self.calls_row = self.rows - 3, self.rows - 2, self.rows - 1
+        self.n, self.bad, self.classes = n, dict(bad or {}), dict(classes or {})
+        self.bad_row, self.xcds, self.ms, self.physical = bad_row, xcds, ms, physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def scratch_last_error(self) -> bytes:
+        return self.err
+
+    def scratch_device_count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def scratch_slots(self) -> int:
+        return self.SLOTS
+
+    def scratch_rows(self) -> int:
+        return self.rows
+
+    def _simd(self, wave: int) -> int:
+        block = wave // 4
+        cu = block // self.xcds % 32
+        return ((((block % self.xcds) << 7) | ((cu // 8) << 5) | (cu % 8)) << 2) | (wave % 4)
+
+    def scratch_test(self, device, rows, nrows, blocks, iso_blocks, rounds, reps, seed, inject_row,
+                     inject_wave, inject_round, inject_alias, inject_stale_word, errors, words, ms, first, frame_bytes,
+                     info, simd_map):
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return -1
+            device = self.physical
+        self.calls.append(f"scratch{device}")
+        chosen = [rows[i] for i in range(nrows)] if 1 <= nrows <= self.rows else []
+        if not 0 <= device < self.n or not 1 <= rounds <= 16 or reps < 1 \
+                or blocks < 0 or iso_blocks < 0 or not chosen or not all(0 <= k < self.rows for k in chosen):
+            self.err = (b"scratch: need a valid device, rounds 1..16, reps >= 1 and a list of known rows")
+            return -2
+        cus = self.xcds * 32
+        grid = blocks or cus
+        iso_grid = iso_blocks or min(2 * cus * 32 // 4, 4096)
+        if iso_grid * 4 > 16384 or grid > 4096:
+            self.err = (b"scratch: the isolate grid may have at most 16384 waves (4096 workgroups: the wave's field of the "
+                        b"written word has 14 bits), not %d workgroups; the frames grid at most 4096 workgroups"
+                        % iso_grid)
+            return -2
+        if inject_row >= 0 and inject_row not in chosen:
+            self.err = b"scratch: inject_row must be in the list"
+            return -2
+        if inject_row >= 0:
+            iso = inject_row == self.iso
+            waves = (iso_grid if iso else grid) * 4
+            if not 0 <= inject_wave < waves or (not iso and (inject_alias or inject_stale_word >= 0 or inject_round != 0)) \
+                    or not 0 <= inject_round < rounds or (inject_alias and inject_wave + 1 >= waves) \
+                    or inject_stale_word >= 256 or (inject_stale_word >= 0 and inject_round < 1) \
+                    or (inject_alias and inject_stale_word >= 0):
+                self.err = (b"scratch: inject_wave must lie inside the row's grid (an alias needs wave + 1 there too), "
+                            b"inject_round inside the rounds, inject_stale_word inside the frame and in a round >= 1 (round 0 "
+                            b"has no round before), one hook at a time, and only the isolate row has the alias and stale "
+                            b"hooks and rounds")
+                return -2
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        for j in range(8):
+            info[j] = 0
+        info[3], info[4], info[5] = iso_grid * 4, grid, iso_grid
+        classes = {"alias": 1, "stale": 2, "corrupt": 3}
+        for k in range(self.rows):
+            on = k in chosen
+            errors[k] = words[k] = 0
+            for j in range(10):
+                first[10 * k + j] = 0
+            first[10 * k] = (1 << 64) - 1
+            frame_bytes[k] = 0
+            ms[k] = self.ms if on else 0.0
+            if not on:
+                continue
+            waves = (iso_grid if k == self.iso else grid) * 4
+            for w in range(waves):
+                simd_map[3 * self._simd(w)] += reps + 1
+                simd_map[3 * self._simd(w) + 2] += 1000 * (reps + 1)
+            if k == self.iso:
+                per, frame_bytes[k] = waves * 64 * 256 * rounds, self.FRAME["isolate"]
+                info[0] = min(waves, cus * 32 // 2)  # half the slots: a 1 KiB frame halves nothing, the fake just says so
+                info[1] = info[2] = cus * 32 * 64 * 1040
+            else:
+                per, frame_bytes[k] = waves * 64 * 17, self.FRAME["index" if k == self.index else "calls"]
+            words[k] = per * (reps + 1)
+            record = None  # where, wave, word, got, want, class, age, writer wave, writer row, launch
+            wrong = self.bad.get((device, k), 0)
+            if wrong:
+                cls = classes[self.classes.get(k, "corrupt")] if k == self.iso else 3
+                cell = (1 << 28) | (3 << 14) | (9 << 8) | 37 if k == self.iso else 37
+                record = ((self.bad_row << 16) | 9, 3, cell, self.WANT ^ 0x100, self.WANT, cls, 1 if cls == 2 else 0,
+                          4 if cls == 1 else (1 << 64) - 1, self._simd(4) if cls == 1 else 0, 1)
+                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+                simd_map[3 * self.bad_row + 1] += wrong
+            if k == inject_row:
+                row = self._simd(inject_wave)
+                if inject_alias:
+                    cls, age, writer, wrow = 1, 0, inject_wave + 1, self._simd(inject_wave + 1)
+                elif inject_stale_word >= 0:
+                    cls, age, writer, wrow = 2, 1, (1 << 64) - 1, 0
+                else:
+                    cls, age, writer, wrow = 3, 0, (1 << 64) - 1, 0
+                word = max(inject_stale_word, 0)
+                cell = (inject_round << 28) | (inject_wave << 14) | word if k == self.iso else 0
+                got = self.WANT ^ 0x10 if cls == 3 else self.WANT ^ 0x5A5A5A5A
+                record = ((row << 16) | 0, inject_wave, cell, got, self.WANT, cls, age, writer, wrow, 0)
+                wrong += 1
+                simd_map[3 * row + 1] += 1
+            errors[k] = wrong
+            if record:
+                for j, v in enumerate(record):
+                    first[10 * k + j] = v
+        return 0
+
+
 def matrix_c_exports() -> Dict[str, List[str]]:
     """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
     :func:`xgmi_c_exports` reads xgmi.hip."""
@@ -1831,9 +1984,9 @@ class NarrowedDiagLib:
 def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = None, atomics: Optional[Dict] = None,
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
             vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, ifetch: Optional[Dict] = None,
-            handoff: Optional[Dict] = None, **diag_kw) -> None:
+            handoff: Optional[Dict] = None, scratch: Optional[Dict] = None, **diag_kw) -> None:
     """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``; ``ops.handoff``: ``FakeHandoffLib(n, **handoff)``)
+    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``; ``ops.handoff``: ``FakeHandoffLib(n, **handoff)``; ``ops.scratch``: ``FakeScratchLib(n, **scratch)``)
     use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
     ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
     ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
@@ -1878,3 +2031,6 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import handoff as handoff_mod
     holib = FakeHandoffLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(handoff or {}))
     handoff_mod.lib = lambda: holib
+    from ..ops import scratch as scratch_mod
+    sclib = FakeScratchLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(scratch or {}))
+    scratch_mod.lib = lambda: sclib
