@@ -58,6 +58,7 @@ from ..models.health import (HEALTHY, UNHEALTHY, UNHEALTHY_TAINT, UNKNOWN, XGMI_
 from ..models.baseline import Baselines, epoch_of, gpu_key
 from ..models.node import HEALTH_ANNOTATION
 from ..models.resources import PRIMARY_GPU_KEY, gpu_breakdown
+from ..ops.optin import OPT_IN, add_flags, chosen
 from .isolation import ISOLATION, Job, Workers
 from .server import _metrics, serve, tls_context  # noqa: F401  (the agent's HTTP side; re-exported)
 
@@ -444,22 +445,17 @@ class Agent:
                  label_node: bool = False, annotation_encoding: str = "json", diag_parallel: int = DIAG_PARALLEL,
                  diag_baseline: bool = True, baseline_file: Optional[str] = None, isolation: str = "thread",
                  diag_setup: Optional[tuple] = None, diag_xgmi_kernel: bool = False,
-                 diag_atomics: bool = False, diag_lanes: bool = False,
-                 diag_scalar: bool = False, diag_matrix: bool = False, diag_vmem: bool = False,
-                 diag_cvt: bool = False, diag_hbmscan: bool = False, diag_ifetch: bool = False,
-                 diag_handoff: bool = False, diag_scratch: bool = False):
+                 diag_extra: Sequence[str] = (), **diag_flags: bool):
         self.node = node
-        self.diag_scratch = diag_scratch  # every device's suite also runs the scratch diagnostic (ops/scratch.py)
-        self.diag_handoff = diag_handoff  # every device's suite also runs the handoff diagnostic (ops/handoff.py)
-        self.diag_ifetch = diag_ifetch  # every device's suite also runs the ifetch diagnostic (ops/ifetch.py)
-        # every device's suite also runs the hbmscan diagnostic (ops/hbmscan.py): it holds the GPU's free memory
-        self.diag_hbmscan = diag_hbmscan
-        self.diag_vmem = diag_vmem  # every device's suite also runs the vmem diagnostic (ops/vmem.py)
-        self.diag_cvt = diag_cvt  # every device's suite also runs the cvt diagnostic (ops/cvt.py)
-        self.diag_matrix = diag_matrix  # every device's suite also runs the matrix diagnostic (ops/matrix.py)
-        self.diag_lanes = diag_lanes  # every device's suite also runs the lanes diagnostic (ops/lanes.py)
-        self.diag_scalar = diag_scalar  # every device's suite also runs the scalar diagnostic (ops/scalar.py)
-        self.diag_atomics = diag_atomics  # every device's suite also runs the atomics diagnostic (ops/atomics.py)
+        # the opt-in diagnostics every device's suite also runs (ops/optin.py), in table order; ``diag_<name>=True``
+        # asks for one by keyword, as ``--diag-<name>`` does
+        for key in diag_flags:
+            if not key.startswith("diag_") or key[5:] not in OPT_IN:
+                raise TypeError(f"Agent.__init__() got an unexpected keyword argument {key!r}")
+        wanted = set(diag_extra) | {key[5:] for key, on in diag_flags.items() if on}
+        if not wanted <= set(OPT_IN):
+            raise ValueError(f"diag_extra must name opt-in diagnostics, not {sorted(wanted - set(OPT_IN))}")
+        self.diag_extra = tuple(name for name in OPT_IN if name in wanted)
         self.diag_xgmi_kernel = diag_xgmi_kernel  # the node-level suite also runs the kernel-driven xGMI passes
         if isolation not in ISOLATION:
             raise ValueError(f"isolation must be one of {ISOLATION}")
@@ -905,13 +901,8 @@ class Agent:
         # the host-link turn is waited for only within this device's watchdog (a GPU stuck in its turn is that
         # GPU's hang, not every GPU's); CLOCK_MONOTONIC is one clock for the agent and its children
         kw["deadline"] = time.monotonic() + 0.9 * self.diag_timeout
-        extra = tuple(t for t, on in (("atomics", self.diag_atomics), ("lanes", self.diag_lanes),
-                                         ("scalar", self.diag_scalar), ("matrix", self.diag_matrix),
-                                         ("vmem", self.diag_vmem), ("cvt", self.diag_cvt),
-                                         ("hbmscan", self.diag_hbmscan), ("ifetch", self.diag_ifetch),
-                                         ("handoff", self.diag_handoff), ("scratch", self.diag_scratch)) if on)
-        if extra:
-            kw["extra"] = extra
+        if self.diag_extra:
+            kw["extra"] = self.diag_extra
         job = self.workers.device(self.diag_level, d, kw, self._diag_done, host)
         self._diag_threads[d] = _DiagRun(job, time.time(), time.monotonic())
 
@@ -1188,46 +1179,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--diag-xgmi-kernel", action="store_true",
                     help="level 2: after the xGMI copy passes, load the links from a kernel too (CU stores and loads), "
                          "and say of every slow copy whether the link or the copy engine was slow")
-    ap.add_argument("--diag-atomics", action="store_true",
-                    help="every GPU's diagnostics also run the atomics test: atomic adds, max, xor and returning adds "
-                         "from every XCD onto one array, every element checked")
-    ap.add_argument("--diag-lanes", action="store_true",
-                    help="every GPU's diagnostics also run the lanes test: every lane-crossing instruction of a wave "
-                         "(DPP, permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane) checked bit for bit, "
-                         "wrong lanes located to their SIMD")
-    ap.add_argument("--diag-scalar", action="store_true",
-                    help="every GPU's diagnostics also run the scalar test: every scalar-ALU instruction against the "
-                         "host's model, the SGPR file of every SIMD under patterns and every width of scalar load, "
-                         "wrong words located to their SIMD")
-    ap.add_argument("--diag-matrix", action="store_true",
-                    help="every GPU's diagnostics also run the matrix test: every MFMA family of the matrix cores on "
-                         "exact operands, every accumulator element checked bit for bit, wrong elements located to "
-                         "their SIMD")
-    ap.add_argument("--diag-vmem", action="store_true",
-                    help="every GPU's diagnostics also run the vmem test: every vector load and store form against the "
-                         "host's model, the buffer descriptor's range check, the vector L1 of every CU and the LDS-DMA "
-                         "loads, wrong words located to their SIMD")
-    ap.add_argument("--diag-cvt", action="store_true",
-                    help="every GPU's diagnostics also run the cvt test: every format conversion of the vector ALU "
-                         "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
-                         "wrong words located to their SIMD")
-    ap.add_argument("--diag-ifetch", action="store_true",
-                    help="every GPU's diagnostics also run the ifetch test: a data-dependent walk over more code than "
-                         "the instruction cache holds and every branch instruction, checked bit for bit against the "
-                         "host's model, wrong words located to the SIMD that executed")
-    ap.add_argument("--diag-handoff", action="store_true",
-                    help="every GPU's diagnostics also run the handoff test: hand-offs between workgroups inside one "
-                         "launch, across XCDs and inside one, in four forms, every word checked bit for bit, a wrong one "
-                         "classified stale or corrupt; every spin is bounded and a wait that ran out is reported, not failed")
-    ap.add_argument("--diag-scratch", action="store_true",
-                    help="every GPU's diagnostics also run the scratch test: private memory -- twice the device's wave "
-                         "slots of 1 KiB-per-lane frames written, held and read back, a wrong word classified alias, "
-                         "stale or corrupt, and the compiler's own locals and call frames")
-    ap.add_argument("--diag-hbmscan", action="store_true",
-                    help="every GPU's diagnostics also run the hbmscan test: every free byte of the GPU's memory but a "
-                         "2 GiB reserve through four phases, every 16-byte word checked, wrong words named (stuck bit, "
-                         "alias, region, scattered); it holds the GPU's free memory while it runs and stops by itself "
-                         "at half of what --diag-timeout leaves it (reported incomplete, not failed)")
+    add_flags(ap, "diag-", "every GPU's diagnostics also run the {name} test")
     ap.add_argument("--diag-isolation", choices=ISOLATION, default="process",
                     help="process (default): each cycle's HIP diagnostics run in disposable child processes, so the "
                          "agent never initialises HIP, a hung one is SIGKILLed at --diag-timeout and a GPU fault "
@@ -1295,10 +1247,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                   annotation_encoding=args.annotation_encoding, diag_parallel=args.diag_parallel,
                   diag_baseline=args.diag_baseline, baseline_file=args.diag_baseline_file,
                   isolation=args.diag_isolation, diag_xgmi_kernel=args.diag_xgmi_kernel,
-                  diag_atomics=args.diag_atomics, diag_lanes=args.diag_lanes,
-                  diag_scalar=args.diag_scalar, diag_matrix=args.diag_matrix, diag_vmem=args.diag_vmem,
-                  diag_cvt=args.diag_cvt, diag_hbmscan=args.diag_hbmscan, diag_ifetch=args.diag_ifetch,
-                  diag_handoff=args.diag_handoff, diag_scratch=args.diag_scratch)
+                  diag_extra=chosen(args, "diag_"))
     if args.diag_baseline_reset and agent.baselines is not None:
         spec = args.diag_baseline_reset.strip()
         gone = agent.baselines.drop(None if spec.lower() == "all" else spec.split(","))

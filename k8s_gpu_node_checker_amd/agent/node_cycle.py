@@ -16,15 +16,15 @@ import json
 import sys
 import threading
 import time
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence
+
+from ..ops.optin import add_flags, chosen
 
 
 def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: int = 8,
-        fabric: bool = True, xgmi_kernel: bool = False, atomics: bool = False, lanes: bool = False,
-        scalar: bool = False, matrix: bool = False, vmem: bool = False, cvt: bool = False,
-        hbmscan: bool = False, ifetch: bool = False, handoff: bool = False,
-        scratch: bool = False) -> Dict[str, Any]:
-    """The cycle; returns the summary (never raises for a failed test: failures are in the result)."""
+        fabric: bool = True, xgmi_kernel: bool = False, extra: Sequence[str] = ()) -> Dict[str, Any]:
+    """The cycle; returns the summary (never raises for a failed test: failures are in the result).  ``extra``: the
+    opt-in diagnostics (``ops/optin.OPT_IN``) every device's suite also runs."""
     from ..ops import diag
     from .agent import Agent
     t0 = time.monotonic()
@@ -46,11 +46,7 @@ def run(devices: List[int], level: int = 1, timeout_s: float = 150.0, parallel: 
     diag.run = counted  # type: ignore[assignment]
     try:
         ag = Agent("node-cycle", source="auto", diag_level=level, devices=list(devices), diag_when="always",
-                   diag_timeout=timeout_s, diag_parallel=parallel, **({"diag_atomics": True} if atomics else {}), **({"diag_lanes": True} if lanes else {}),
-                   **({"diag_scalar": True} if scalar else {}), **({"diag_matrix": True} if matrix else {}),
-                   **({"diag_vmem": True} if vmem else {}), **({"diag_cvt": True} if cvt else {}),
-                   **({"diag_hbmscan": True} if hbmscan else {}), **({"diag_ifetch": True} if ifetch else {}),
-                   **({"diag_handoff": True} if handoff else {}), **({"diag_scratch": True} if scratch else {}))
+                   diag_timeout=timeout_s, diag_parallel=parallel, diag_extra=extra)
         rep = ag.probe_once()
     finally:
         diag.run = real_run  # type: ignore[assignment]
@@ -92,30 +88,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--no-fabric", dest="fabric", action="store_false")
     ap.add_argument("--xgmi-kernel", dest="xgmi_kernel", action="store_true",
                     help="also load the xGMI links from a kernel and attribute slow copies to link or copy engine")
-    ap.add_argument("--atomics", action="store_true",
-                    help="also run the atomics diagnostic on every device (ops/atomics.py)")
-    ap.add_argument("--lanes", action="store_true",
-                    help="also run the lanes diagnostic on every device (ops/lanes.py)")
-    ap.add_argument("--scalar", action="store_true",
-                    help="also run the scalar diagnostic on every device (ops/scalar.py)")
-    ap.add_argument("--matrix", action="store_true",
-                    help="also run the matrix diagnostic on every device (ops/matrix.py)")
-    ap.add_argument("--vmem", action="store_true",
-                    help="also run the vmem diagnostic on every device (ops/vmem.py)")
-    ap.add_argument("--cvt", action="store_true",
-                    help="also run the cvt diagnostic on every device (ops/cvt.py)")
-    ap.add_argument("--hbmscan", action="store_true",
-                    help="also run the hbmscan diagnostic on every device (ops/hbmscan.py)")
-    ap.add_argument("--ifetch", action="store_true",
-                    help="also run the ifetch diagnostic on every device (ops/ifetch.py)")
-    ap.add_argument("--handoff", action="store_true",
-                    help="also run the handoff diagnostic on every device (ops/handoff.py)")
-    ap.add_argument("--scratch", action="store_true",
-                    help="also run the scratch diagnostic on every device (ops/scratch.py)")
+    add_flags(ap, "", "also run the {name} diagnostic on every device")
     args = ap.parse_args(argv)
     devices = [int(x) for x in args.devices.split(",") if x.strip()]
-    res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel, args.atomics, args.lanes,
-              args.scalar, args.matrix, args.vmem, args.cvt, args.hbmscan, args.ifetch, args.handoff, args.scratch)
+    res = run(devices, args.level, args.timeout, args.parallel, args.fabric, args.xgmi_kernel, chosen(args))
     print(json.dumps(res, separators=(",", ":"), default=str), flush=True)
     return 0
 

@@ -1,6 +1,6 @@
 """Build every native component in-tree (``k8s_gpu_node_checker_amd/_native/``).
 
-``python -m k8s_gpu_node_checker_amd.build [--only fastpath,probe,diag,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff,scratch] [--force]``
+``python -m k8s_gpu_node_checker_amd.build [--only {targets}] [--force]``
 
 =====================  ==================================================  ==========================
 artefact               source                                              toolchain
@@ -10,21 +10,13 @@ artefact               source                                              toolc
 ``mi355x-probe``       ``csrc/probe/probe_main.cpp`` (standalone CLI)       g++ + libamd_smi
 ``libmi355x_diag.so``  ``csrc/diag/diag.hip`` + ``csrc/diag/*.h`` (kernels)   hipcc --offload-arch=gfx950
 ``libmi355x_xgmi.so``  ``csrc/xgmi/xgmi.hip`` (kernel-driven xGMI test)      hipcc --offload-arch=gfx950
-``libmi355x_atomics.so`` ``csrc/atomics/atomics.hip`` (atomics diagnostic)      hipcc --offload-arch=gfx950
-``libmi355x_lanes.so`` ``csrc/lanes/lanes.hip`` (lanes diagnostic)            hipcc --offload-arch=gfx950
-``libmi355x_scalar.so`` ``csrc/scalar/scalar.hip`` (scalar diagnostic)        hipcc --offload-arch=gfx950
-``libmi355x_matrix.so`` ``csrc/matrix/matrix.hip`` (matrix diagnostic)        hipcc --offload-arch=gfx950
-``libmi355x_vmem.so``  ``csrc/vmem/vmem.hip`` (vmem diagnostic)              hipcc --offload-arch=gfx950
-``libmi355x_cvt.so``   ``csrc/cvt/cvt.hip`` (cvt diagnostic)                 hipcc --offload-arch=gfx950
-``libmi355x_hbmscan.so`` ``csrc/hbmscan/hbmscan.hip`` (hbmscan diagnostic)      hipcc --offload-arch=gfx950
-``libmi355x_ifetch.so`` ``csrc/ifetch/ifetch.hip`` (ifetch diagnostic)        hipcc --offload-arch=gfx950
-``libmi355x_handoff.so`` ``csrc/handoff/handoff.hip`` (handoff diagnostic)     hipcc --offload-arch=gfx950
-``libmi355x_scratch.so`` ``csrc/scratch/scratch.hip`` (scratch diagnostic)     hipcc --offload-arch=gfx950
+{opt_in_rows}
 ``libmi355x_fabric.so`` ``csrc/fabric/fabric.hip`` (RCCL over xGMI)         hipcc + /opt/rocm/lib/librccl
 =====================  ==================================================  ==========================
 
-The thirteen HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
-lanes, scalar, matrix, vmem, cvt, ifetch, handoff and scratch also share ``csrc/common/simd_report.h``.
+The HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
+{simd_located} also share ``csrc/common/simd_report.h``.
+The opt-in diagnostics' targets and their rows above are generated from ``ops/optin.OPT_IN``.
 Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
 The ifetch library's one large kernel (more than 400 KiB of code) takes about 40 s to compile, the longest of all.
 
@@ -42,6 +34,8 @@ import sys
 import sysconfig
 from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence
+
+from .ops.optin import OPT_IN
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
@@ -62,8 +56,8 @@ def _targets() -> Dict[str, Dict[str, object]]:
            f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"]
     # every HIP library is built by the same line (fabric adds RCCL after its sources); includes are relative, no -I
     hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
-    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers all thirteen share
-    simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the eight SIMD-located diagnostics
+    hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers every HIP library shares
+    simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the SIMD-located diagnostics
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -105,76 +99,14 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "cmd": hip_cmd,
             "requires": hipcc,
         },
-        "atomics": {
-            "sources": [os.path.join(CSRC, "atomics", "atomics.hip")],
-            "headers": [os.path.join(CSRC, "atomics", "atomics_ref.h"), hip_host],
-            "out": os.path.join(OUT, "libmi355x_atomics.so"),
+        **{name: {  # the opt-in diagnostics (ops/optin.py), one library each
+            "sources": [os.path.join(CSRC, name, f"{name}.hip")],
+            "headers": [os.path.join(CSRC, name, f"{name}_ref.h"), hip_host]
+            + ([simd_report] if entry.simd_report else []),
+            "out": os.path.join(OUT, f"libmi355x_{name}.so"),
             "cmd": hip_cmd,
             "requires": hipcc,
-        },
-        "lanes": {
-            "sources": [os.path.join(CSRC, "lanes", "lanes.hip")],
-            "headers": [os.path.join(CSRC, "lanes", "lanes_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_lanes.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "scalar": {
-            "sources": [os.path.join(CSRC, "scalar", "scalar.hip")],
-            "headers": [os.path.join(CSRC, "scalar", "scalar_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_scalar.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "matrix": {
-            "sources": [os.path.join(CSRC, "matrix", "matrix.hip")],
-            "headers": [os.path.join(CSRC, "matrix", "matrix_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_matrix.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "vmem": {
-            "sources": [os.path.join(CSRC, "vmem", "vmem.hip")],
-            "headers": [os.path.join(CSRC, "vmem", "vmem_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_vmem.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "cvt": {
-            "sources": [os.path.join(CSRC, "cvt", "cvt.hip")],
-            "headers": [os.path.join(CSRC, "cvt", "cvt_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_cvt.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "hbmscan": {
-            "sources": [os.path.join(CSRC, "hbmscan", "hbmscan.hip")],
-            "headers": [os.path.join(CSRC, "hbmscan", "hbmscan_ref.h"), hip_host],
-            "out": os.path.join(OUT, "libmi355x_hbmscan.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "ifetch": {
-            "sources": [os.path.join(CSRC, "ifetch", "ifetch.hip")],
-            "headers": [os.path.join(CSRC, "ifetch", "ifetch_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_ifetch.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "handoff": {
-            "sources": [os.path.join(CSRC, "handoff", "handoff.hip")],
-            "headers": [os.path.join(CSRC, "handoff", "handoff_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_handoff.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
-        "scratch": {
-            "sources": [os.path.join(CSRC, "scratch", "scratch.hip")],
-            "headers": [os.path.join(CSRC, "scratch", "scratch_ref.h"), hip_host, simd_report],
-            "out": os.path.join(OUT, "libmi355x_scratch.so"),
-            "cmd": hip_cmd,
-            "requires": hipcc,
-        },
+        } for name, entry in OPT_IN.items()},
         "fabric": {
             "sources": [os.path.join(CSRC, "fabric", "fabric.hip")],
             "headers": [hip_host],
@@ -184,6 +116,13 @@ def _targets() -> Dict[str, Dict[str, object]]:
             "requires": hipcc,
         },
     }
+
+
+__doc__ = __doc__.format(
+    targets=",".join(_targets()),
+    opt_in_rows="\n".join(f"{f'``libmi355x_{n}.so``':<22} {f'``csrc/{n}/{n}.hip`` ({n} diagnostic)':<51} "
+                          f"hipcc --offload-arch={ARCH}" for n in OPT_IN),
+    simd_located=", ".join(n for n, entry in OPT_IN.items() if entry.simd_report))
 
 
 def _stale(out: str, deps: Sequence[str], cmd: str = "") -> bool:
@@ -245,7 +184,7 @@ def build(only: Optional[Sequence[str]] = None, force: bool = False, verbose: bo
 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--only", help="comma list of fastpath,probe,diag,xgmi,atomics,lanes,scalar,matrix,vmem,cvt,hbmscan,ifetch,handoff,scratch,fabric")
+    ap.add_argument("--only", help="comma list of " + ",".join(_targets()))
     ap.add_argument("--force", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)

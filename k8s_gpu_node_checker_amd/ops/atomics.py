@@ -19,7 +19,7 @@ import ctypes
 import time
 from typing import Any, Dict, Optional, Sequence, Tuple
 
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native kind index (AtomicsKind of atomics_ref.h): index into this
 KINDS = ("add_u32", "add_u64", "add_f32", "add_f64", "pk_bf16", "max_u32", "xor_u32", "ticket")
@@ -47,15 +47,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_atomics.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_atomics.so", _signatures())
     return _lib
 
 
@@ -135,3 +127,12 @@ def atomics_test(device: int = 0, words: int = 16 << 20, adders: int = 8, kinds:
     return {"pass": total == 0, "errors": total, "kinds": rows, "words": int(words), "adders": int(adders),
             "ms": {k: r["ms"] for k, r in rows.items()}, "wall_s": round(time.perf_counter() - t0, 3),
             "detail": "; ".join(problems)}
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    kinds = r.get("kinds") or {}
+    xcds = sorted({v.get("xcds") for v in kinds.values()} - {None})
+    rates = " · ".join(f"{k} {v.get('gbs', 0):.0f}" for k, v in kinds.items())
+    return (f"{r.get('words', '?')} elements x {r.get('adders', '?')} adders from "
+            f"{'/'.join(map(str, xcds)) or '?'} XCDs, {r.get('errors', 0)} wrong; {rates} GB/s")

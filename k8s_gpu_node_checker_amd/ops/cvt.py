@@ -27,7 +27,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native op index (CvtOp of cvt_ref.h): index into OPS
 CLASSIC = ("f16_f32", "f32_f16", "f32_f64", "f64_f32", "i32_f32", "u32_f32", "i32_f64", "u32_f64", "f32_i32", "f32_u32",
@@ -88,15 +88,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_cvt.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_cvt.so", _signatures())
     return _lib
 
 
@@ -173,6 +165,15 @@ def cvt_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_ITE
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows, mode = r.get("ops") or {}, r.get("mode") or {}
+    rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
+    return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+            f"XCDs, round {mode.get('round', '?')} denorm {mode.get('denorm', '?')}, {r.get('errors', 0)} wrong words; "
+            f"{r.get('ms', 0):.1f} ms, mean {rate:.0f} G conversions/s")
 
 
 Row = Tuple[int, ...]

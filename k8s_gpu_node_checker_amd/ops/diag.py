@@ -18,9 +18,11 @@ from __future__ import annotations
 import ctypes
 import threading
 import time
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from importlib import import_module
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
-from .native import NativeUnavailable, load_cdll
+from .native import NativeUnavailable, bind_cdll
+from .optin import OPT_IN, add_flags, chosen
 
 # --- Pass / degraded thresholds --------------------------------------------------------------------
 # Every rate test is judged against the *reference rate* of a healthy, unpartitioned MI355X (256 CUs,
@@ -349,18 +351,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_diag.so", required=True)
-        assert L is not None
-        # every name is looked up here, so a library built from an older tree -- one export per generation of a
-        # diagnostic, no diag_valu_burn or diag_p2p_fan -- raises AttributeError at load instead of being called
-        # with another generation's argument list
-        for name, (argtypes, restype) in _signatures().items():
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_diag.so", _signatures())
     return _lib
 
 
@@ -910,87 +901,18 @@ def valu_burn(device: int = 0, kinds=VALU_KINDS, iters: int = 2000, reps: int = 
                  iters, reps, scale, inject_block)
 
 
-def atomics_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in atomics diagnostic (``ops/atomics.atomics_test``, its own library): every element of an array gets
-    atomic operations from workgroups on every XCD and is checked bit for bit.  No level runs it; ``run(extra=
-    ("atomics",))`` does."""
-    from . import atomics  # lazily: only who asks for the test needs libmi355x_atomics.so
-    return atomics.atomics_test(device, **kw)
+def _opt_in(name: str) -> Callable[..., Dict[str, Any]]:
+    """``<name>_test`` of this module for an entry of ``optin.OPT_IN``: ``ops/<name>.<name>_test``, imported when called
+    (only who asks for the test needs its library)."""
+    def test(device: int = 0, **kw: Any) -> Dict[str, Any]:
+        return getattr(import_module(f"{__package__}.{name}"), f"{name}_test")(device, **kw)
+    test.__name__ = test.__qualname__ = f"{name}_test"
+    test.__doc__ = (f"The opt-in {name} diagnostic (``ops/{name}.{name}_test``, its own library): "
+                    f"{OPT_IN[name].description}.  No level runs it; ``run(extra=({name!r},))`` does.")
+    return test
 
 
-def matrix_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in matrix diagnostic (``ops/matrix.matrix_test``, its own library): every MFMA family of the matrix
-    cores (fp32, fp16, bf16, int8, fp64, bf8, f8f6f4 with and without block scales, sparse) on operands whose sums
-    are exact in any order, every accumulator element checked bit for bit against the host's model.  No level runs it;
-    ``run(extra=("matrix",))`` does."""
-    from . import matrix  # lazily: only who asks for the test needs libmi355x_matrix.so
-    return matrix.matrix_test(device, **kw)
-
-
-def vmem_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in vmem diagnostic (``ops/vmem.vmem_test``, its own library): every vector load and store form as one
-    native instruction in walks checked against the host's model, the buffer descriptor's range check, the vector L1
-    of every CU and the LDS-DMA loads.  No level runs it; ``run(extra=("vmem",))`` does."""
-    from . import vmem  # lazily: only who asks for the test needs libmi355x_vmem.so
-    return vmem.vmem_test(device, **kw)
-
-
-def cvt_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in cvt diagnostic (``ops/cvt.cvt_test``, its own library): every format conversion of the vector ALU
-    (classic, bf16, fp8 / bf8, the gfx950 scalef32 forms) as one native instruction in chains that every lane checks
-    bit for bit against the host's model.  No level runs it; ``run(extra=("cvt",))`` does."""
-    from . import cvt  # lazily: only who asks for the test needs libmi355x_cvt.so
-    return cvt.cvt_test(device, **kw)
-
-
-def ifetch_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in ifetch diagnostic (``ops/ifetch.ifetch_test``, its own library): the front end of every CU -- a
-    data-dependent walk over a code footprint larger than the instruction cache, every constant a literal of the
-    instruction stream, and every branch instruction in scalar chains -- checked bit for bit against the host's
-    model.  No level runs it; ``run(extra=("ifetch",))`` does."""
-    from . import ifetch  # lazily: only who asks for the test needs libmi355x_ifetch.so
-    return ifetch.ifetch_test(device, **kw)
-
-
-def handoff_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in handoff diagnostic (``ops/handoff.handoff_test``, its own library): a ring of ping-pong hand-offs
-    between workgroups inside one launch, across XCDs and inside one -- the L2 write-back, the L1 invalidate,
-    write-through stores, L1-bypassing loads, agent-scope flags and atomic adds -- every word checked bit for bit, a
-    wrong one classified stale or corrupt, every spin bounded.  No level runs it; ``run(extra=("handoff",))`` does."""
-    from . import handoff  # lazily: only who asks for the test needs libmi355x_handoff.so
-    return handoff.handoff_test(device, **kw)
-
-
-def scratch_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in scratch diagnostic (``ops/scratch.scratch_test``, its own library): private memory -- twice the device's wave slots of 1 KiB frames written, held and read
-    back with a wrong word classified alias, stale or corrupt, and the compiler's own locals and call frames.  No level
-    runs it; ``run(extra=("scratch",))`` does."""
-    from . import scratch  # lazily: only who asks for the test needs libmi355x_scratch.so
-    return scratch.scratch_test(device, **kw)
-
-
-def hbmscan_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in hbmscan diagnostic (``ops/hbmscan.hbmscan_test``, its own library): every free byte of the device's
-    memory but a reserve, in chunks, through four phases with every 16-byte word checked, and a named finding
-    (stuck bit, alias, region, scattered).  No level runs it; ``run(extra=("hbmscan",))`` does."""
-    from . import hbmscan  # lazily: only who asks for the test needs libmi355x_hbmscan.so
-    return hbmscan.hbmscan_test(device, **kw)
-
-
-def lanes_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in lanes diagnostic (``ops/lanes.lanes_test``, its own library): every lane-crossing instruction of a
-    wave (DPP, the permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane / readfirstlane) in chains that
-    every lane checks bit for bit against the host's model.  No level runs it; ``run(extra=("lanes",))`` does."""
-    from . import lanes  # lazily: only who asks for the test needs libmi355x_lanes.so
-    return lanes.lanes_test(device, **kw)
-
-
-def scalar_test(device: int = 0, **kw: Any) -> Dict[str, Any]:
-    """The opt-in scalar diagnostic (``ops/scalar.scalar_test``, its own library): the scalar ALU one native
-    instruction per op against the host's model, the SGPR file of every SIMD under patterns, and every width of
-    scalar load through the scalar data cache.  No level runs it; ``run(extra=("scalar",))`` does."""
-    from . import scalar  # lazily: only who asks for the test needs libmi355x_scalar.so
-    return scalar.scalar_test(device, **kw)
+globals().update({f"{name}_test": _opt_in(name) for name in OPT_IN})
 
 
 def _xcd_slices(fn: str, name: str, device: int, slice_bytes: int, passes: int, blocks_per_cu: int, seed: int,
@@ -1294,20 +1216,10 @@ _TESTS: Dict[str, Tuple[str, Dict[str, Any]]] = {
     "gemm": ("gemm", {}), "gemm_fp8": ("gemm_fp8", {}), "hbm": ("hbm", {}), "hbm_xcd": ("hbm_xcd", {}),
     "memtest": ("memtest", {}), "mfma": ("mfma_burn", {}), "lds": ("lds_test", {}), "l2": ("l2_bandwidth", {}),
     "valu": ("valu_burn", {}), "regfile": ("regfile_test", {}), "host_link": ("host_link", {}),
-    "atomics": ("atomics_test", {}),  # in no level: run(extra=("atomics",))
-    "lanes": ("lanes_test", {}),  # in no level: run(extra=("lanes",))
-    "scalar": ("scalar_test", {}),  # in no level: run(extra=("scalar",))
-    "matrix": ("matrix_test", {}),  # in no level: run(extra=("matrix",))
-    "vmem": ("vmem_test", {}),  # in no level: run(extra=("vmem",))
-    "cvt": ("cvt_test", {}),  # in no level: run(extra=("cvt",))
-    "hbmscan": ("hbmscan_test", {}),  # in no level: run(extra=("hbmscan",))
-    "ifetch": ("ifetch_test", {}),  # in no level: run(extra=("ifetch",))
-    "handoff": ("handoff_test", {}),  # in no level: run(extra=("handoff",))
-    "scratch": ("scratch_test", {}),  # in no level: run(extra=("scratch",))
+    **{name: (f"{name}_test", {}) for name in OPT_IN},  # in no level: run(extra=(name,))
 }
 # error counts only: nothing to scale
-_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test", "atomics_test", "lanes_test", "scalar_test", "matrix_test",
-                       "vmem_test", "cvt_test", "hbmscan_test", "ifetch_test", "handoff_test", "scratch_test"))
+_UNSCALED = frozenset(("memtest", "lds_test", "regfile_test")) | {f"{name}_test" for name in OPT_IN}
 # share of what is left of run()'s deadline that the hbmscan may use (as P2P_SHARE for the xGMI matrix): it stops by
 # itself there and reports ``complete`` false, instead of being killed by the agent's watchdog with nothing to show
 HBMSCAN_SHARE = 0.5
@@ -1374,8 +1286,8 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
         deadline: Optional[float] = None, extra: Sequence[str] = (),
         options: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, Dict[str, Any]]:
     """Run the diagnostics of ``level`` on ``device`` (1 = ~1 s quick check, 2 = deep, 3 = deep plus
-    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (``"atomics"``, ``"lanes"``, ``"scalar"``, ``"matrix"``, ``"vmem"``, ``"cvt"``, ``"hbmscan"``, ``"ifetch"``, ``"handoff"``, ``"scratch"``),
-    each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
+    the vector ALU burn-in and the register-file test), then the opt-in tests named in ``extra`` (names of
+    ``optin.OPT_IN``), each treated as the level's own are.  ``options``: keyword arguments for single tests, by name
     (``{"hbmscan": {"gib": 64}}``).  With a ``deadline`` the hbmscan gets ``HBMSCAN_SHARE`` of what is left of it.
 
     ``scale`` defaults to the device's own share of a full MI355X (:func:`device_scale`).  A rate that
@@ -1428,7 +1340,9 @@ def run(level: int = 1, device: int = 0, scale: Optional[Scale] = None,
 
 
 def _summary(test: str, r: Dict[str, Any]) -> str:
-    """One line of numbers for a test result (render_text)."""
+    """One line of numbers for a test result (render_text); an opt-in test's own module writes its line."""
+    if test in OPT_IN:
+        return import_module(f"{__package__}.{test}").summary(r)
     if test in ("gemm", "gemm_fp8"):
         return f"{r.get('tflops', 0):.0f} TFLOP/s" + (f" ({r['fraction']:.0%} of reference)" if "fraction" in r else "")
     if test == "hbm":
@@ -1443,75 +1357,6 @@ def _summary(test: str, r: Dict[str, Any]) -> str:
         m = r.get("map") or {}
         kinds = " · ".join(f"{k} {v.get('gops', 0):.0f}" for k, v in (r.get("kinds") or {}).items())
         return f"{kinds} GOP/s; {m.get('cus', '?')} CUs, XCD spread {m.get('slowest_rel', 1.0):.3f}"
-    if test == "atomics":
-        kinds = r.get("kinds") or {}
-        xcds = sorted({v.get("xcds") for v in kinds.values()} - {None})
-        rates = " · ".join(f"{k} {v.get('gbs', 0):.0f}" for k, v in kinds.items())
-        return (f"{r.get('words', '?')} elements x {r.get('adders', '?')} adders from "
-                f"{'/'.join(map(str, xcds)) or '?'} XCDs, {r.get('errors', 0)} wrong; {rates} GB/s")
-    if test == "lanes":
-        rows = r.get("ops") or {}
-        rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
-        return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
-                f"XCDs, {r.get('errors', 0)} wrong lanes; {r.get('ms', 0):.1f} ms, mean {rate:.0f} G crossings/s")
-    if test == "matrix":
-        rows = r.get("ops") or {}
-        return (f"{len(rows)} ops x {r.get('iters', '?')} rounds on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
-                f"XCDs, {r.get('errors', 0)} wrong elements; {r.get('ms', 0):.1f} ms")
-    if test == "vmem":
-        rows, b, l1, dma = r.get("ops") or {}, r.get("bounds") or {}, r.get("l1") or {}, r.get("ldsdma") or {}
-        return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
-                f"{len(b.get('rows') or {})} bounds rows, L1 {l1.get('slice_bytes', '?')} B x {l1.get('passes', '?')} passes "
-                f"(sc1 / plain {l1.get('l1_gain', 0):.2f}), {len(dma.get('forms') or {})} LDS-DMA forms, "
-                f"{r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
-    if test == "cvt":
-        rows, mode = r.get("ops") or {}, r.get("mode") or {}
-        rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
-        return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
-                f"XCDs, round {mode.get('round', '?')} denorm {mode.get('denorm', '?')}, {r.get('errors', 0)} wrong words; "
-                f"{r.get('ms', 0):.1f} ms, mean {rate:.0f} G conversions/s")
-    if test == "ifetch":
-        p = r.get("parts") or {}
-        walk, br = p.get("walk") or {}, p.get("branch") or {}
-        rows = walk.get("rows") or {}
-        feet = [v.get("footprint_bytes", 0) for v in rows.values()]
-        span = f"{min(feet) / 1024:.0f}-{max(feet) / 1024:.0f} KiB of code" if feet else "no rows"
-        per = "/".join(f"{v.get('ns_per_block', 0):.0f}" for v in rows.values())
-        return (f"walk {len(rows)} footprints ({span}) x {walk.get('steps', '?')} blocks per wave ({per} ns per block), "
-                f"{len(br.get('ops') or {})} branch ops x {br.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of "
-                f"{r.get('xcds', '?')} XCDs, {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
-    if test == "handoff":
-        rows = r.get("rows") or {}
-        per = "/".join(f"{v.get('us_per_round', 0):.1f}" for v in rows.values())
-        waits = sum(v.get("timeouts", 0) for v in rows.values())
-        state = "" if r.get("complete", True) else f", incomplete ({waits} waits ran out: re-run on an idle device)"
-        return (f"{len(rows)} rows x {r.get('rounds', '?')} rounds on {r.get('blocks', '?')} workgroups, {r.get('simds', '?')} "
-                f"SIMDs of {r.get('xcds', '?')} XCDs ({per} us per round), {r.get('errors', 0)} wrong words{state}; "
-                f"{r.get('ms', 0):.1f} ms")
-    if test == "scratch":
-        rows = r.get("rows") or {}
-        return (f"{len(rows)} rows ({', '.join(rows)}) on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
-                f"{r.get('isolate_waves', '?')} isolate waves x {r.get('rounds', '?')} rounds ({r.get('co_resident_waves', '?')} "
-                f"frames live at once), {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
-    if test == "hbmscan":
-        from .hbmscan import finding_text
-        state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
-        return (f"{r.get('tested_gib', 0):.4g} of {r.get('total_gib', 0):.4g} GiB ({r.get('coverage', 0):.1%}) in "
-                f"{r.get('chunks', '?')} chunks{state}, {r.get('errors', 0)} wrong words, finding "
-                f"{finding_text(r.get('finding') or {'kind': 'none'})}; {r.get('wall_s', 0):.1f} s")
-    if test == "scalar":
-        p = r.get("parts") or {}
-        salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
-        said = []
-        if salu:
-            said.append(f"{len(salu.get('ops') or {})} ops x {salu.get('iters', '?')} steps {salu.get('errors', 0)} wrong")
-        if sgpr:
-            said.append(f"{sgpr.get('regs_per_wave', '?')} SGPRs x {(sgpr.get('waves_per_simd') or {}).get('max', 0):g} "
-                        f"waves per SIMD {sgpr.get('errors', 0)} wrong")
-        if smem:
-            said.append(f"{len(smem.get('kinds') or {})} load kinds {smem.get('errors', 0)} wrong")
-        return (f"{'; '.join(said) or 'no part'}; {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
-                f"{r.get('ms', 0):.1f} ms")
     if test == "regfile":
         return (f"{r.get('simds', '?')} SIMDs x {r.get('bytes_per_simd', 0) // 1024} KiB "
                 f"({r.get('regs_per_lane', '?')} registers), {r.get('errors', 0)} bad words")
@@ -1703,9 +1548,10 @@ def burn_in(level: int, devices: List[int], minutes: float, parallel: int = 8,
 
 def main(argv=None) -> int:
     """``mi355x-diag [--level N] [--device D] [--parallel P] [--timeout S] [--duration MIN] [--xgmi-kernel]
-    [--atomics] [--lanes] [--scalar] [--matrix] [--vmem] [--cvt] [--hbmscan [--hbmscan-gib N]] [--ifetch] [--handoff] [--scratch] [--format json|text]``:
+    [--<opt-in diagnostic>]... [--hbmscan-gib N] [--format json|text]``:
     run the active diagnostics (every device at once, as the node agent does), print one JSON document (or a
-    text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes."""
+    text summary); ``--duration`` turns it into an acceptance burn-in of that many minutes.  One flag per entry of
+    ``optin.OPT_IN`` adds that diagnostic."""
     import argparse
     import json
     ap = argparse.ArgumentParser(prog="mi355x-diag", description="MI355X active diagnostics (HIP, gfx950)")
@@ -1719,47 +1565,7 @@ def main(argv=None) -> int:
     ap.add_argument("--xgmi-kernel", dest="xgmi_kernel", action="store_true",
                     help="level 2: also load the xGMI links from a kernel (CU stores and loads) and say of every slow "
                          "copy whether the link or the copy engine was slow")
-    ap.add_argument("--atomics", action="store_true",
-                    help="also run the atomics diagnostic on every device: atomic adds, max, xor and returning adds "
-                         "from every XCD onto one array, every element checked (ops/atomics.py)")
-    ap.add_argument("--lanes", action="store_true",
-                    help="also run the lanes diagnostic on every device: every lane-crossing instruction of a wave "
-                         "(DPP, permlane swaps, ds_swizzle / ds_bpermute / ds_permute, readlane) checked bit for bit "
-                         "against the host's model, wrong lanes located to their SIMD (ops/lanes.py)")
-    ap.add_argument("--scalar", action="store_true",
-                    help="also run the scalar diagnostic on every device: every scalar-ALU instruction against the "
-                         "host's model, the SGPR file of every SIMD under patterns, every width of scalar load "
-                         "through the scalar data cache (ops/scalar.py)")
-    ap.add_argument("--matrix", action="store_true",
-                    help="also run the matrix diagnostic on every device: every MFMA family of the matrix cores "
-                         "(fp32, fp16, bf16, int8, fp64, bf8, f8f6f4, sparse) on exact operands, every "
-                         "accumulator element checked bit for bit against the host's model (ops/matrix.py)")
-    ap.add_argument("--vmem", action="store_true",
-                    help="also run the vmem diagnostic on every device: every vector load and store form against the "
-                         "host's model, the buffer descriptor's range check, the vector L1 of every CU and the "
-                         "LDS-DMA loads (ops/vmem.py)")
-    ap.add_argument("--cvt", action="store_true",
-                    help="also run the cvt diagnostic on every device: every format conversion of the vector ALU "
-                         "(classic, bf16, fp8 / bf8, the scalef32 forms) checked bit for bit against the host's model, "
-                         "wrong words located to their SIMD (ops/cvt.py)")
-    ap.add_argument("--ifetch", action="store_true",
-                    help="also run the ifetch diagnostic on every device: a data-dependent walk over more code than the "
-                         "instruction cache holds and every branch instruction, checked bit for bit against the host's "
-                         "model, wrong words located to the SIMD that executed (ops/ifetch.py)")
-    ap.add_argument("--handoff", action="store_true",
-                    help="also run the handoff diagnostic on every device: a ring of hand-offs between workgroups inside "
-                         "one launch, across XCDs and inside one, in four forms (release / acquire fences, write-through "
-                         "stores, an atomic counter, tagged granules), every word checked bit for bit, a wrong one "
-                         "classified stale or corrupt, every spin bounded (ops/handoff.py)")
-    ap.add_argument("--scratch", action="store_true",
-                    help="also run the scratch diagnostic on every device: private memory -- twice the device's "
-                         "wave slots of 1 KiB-per-lane frames written, held and read back, a wrong word classified alias, "
-                         "stale or corrupt; the compiler's own locals and call frames, compared bit for bit with the "
-                         "host's run (ops/scratch.py)")
-    ap.add_argument("--hbmscan", action="store_true",
-                    help="also run the hbmscan diagnostic on every device: every free byte of its memory but a 2 GiB "
-                         "reserve through four phases, every 16-byte word checked, and a named finding (stuck bit, "
-                         "alias, region, scattered); holds the GPU's free memory while it runs (ops/hbmscan.py)")
+    add_flags(ap, "", "also run the {name} diagnostic on every device")
     ap.add_argument("--hbmscan-gib", type=float, default=None, metavar="N",
                     help="with --hbmscan: test N GiB instead of all free memory (under 2 GiB the caches may answer)")
     ap.add_argument("--timeout", type=float, default=0.0,
@@ -1775,11 +1581,7 @@ def main(argv=None) -> int:
                                                                                 "error": msg}, indent=1))
         return 1
     xk = {"kernel": True} if args.xgmi_kernel else {}  # opt-in: without the flag fabric_tests is called as ever
-    opt_in = tuple(t for t, on in (("atomics", args.atomics), ("lanes", args.lanes), ("scalar", args.scalar),
-                                             ("matrix", args.matrix), ("vmem", args.vmem), ("cvt", args.cvt),
-                                             ("hbmscan", args.hbmscan), ("ifetch", args.ifetch),
-                                             ("handoff", args.handoff), ("scratch", args.scratch))
-                   if on)
+    opt_in = chosen(args)
     more: Dict[str, Any] = {"extra": opt_in} if opt_in else {}  # likewise run_devices and burn_in
     if args.hbmscan and args.hbmscan_gib is not None:
         more["options"] = {"hbmscan": {"gib": args.hbmscan_gib}}

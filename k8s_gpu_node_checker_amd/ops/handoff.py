@@ -37,7 +37,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name, slot_name
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native row index is FORMS.index(form) * 2 + PLACEMENTS.index(placement) (handoff_ref.h)
 FORMS = ("fence", "wt", "wt_add", "granule")
@@ -77,15 +77,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_handoff.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_handoff.so", _signatures())
     return _lib
 
 
@@ -205,3 +197,14 @@ def handoff_test(device: int = 0, rows: Sequence[str] = ROWS, rounds: int = DEFA
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows = r.get("rows") or {}
+    per = "/".join(f"{v.get('us_per_round', 0):.1f}" for v in rows.values())
+    waits = sum(v.get("timeouts", 0) for v in rows.values())
+    state = "" if r.get("complete", True) else f", incomplete ({waits} waits ran out: re-run on an idle device)"
+    return (f"{len(rows)} rows x {r.get('rounds', '?')} rounds on {r.get('blocks', '?')} workgroups, {r.get('simds', '?')} "
+            f"SIMDs of {r.get('xcds', '?')} XCDs ({per} us per round), {r.get('errors', 0)} wrong words{state}; "
+            f"{r.get('ms', 0):.1f} ms")

@@ -21,7 +21,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native indices (HbmscanPhase, HbmscanFindingKind of hbmscan_ref.h): index into these
 PHASES = ("addr", "invert", "random", "fade")
@@ -74,15 +74,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_hbmscan.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_hbmscan.so", _signatures())
     return _lib
 
 
@@ -247,3 +239,11 @@ def hbmscan_test(device: int = 0, gib: Optional[float] = None, reserve_mib: floa
             "complete": bool(complete), "reached": {"phase": PHASES[rph], "step": rst},
             "phases": phases, "records": records, "hist": {str(i): int(hist[i]) for i in range(HIST) if hist[i]},
             "finding": finding, "wall_s": round(time.perf_counter() - t0, 3), "detail": "; ".join(said)}
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    state = ("" if r.get("complete", True) else ", incomplete") + (", cached: cells not proven" if r.get("cached") else "")
+    return (f"{r.get('tested_gib', 0):.4g} of {r.get('total_gib', 0):.4g} GiB ({r.get('coverage', 0):.1%}) in "
+            f"{r.get('chunks', '?')} chunks{state}, {r.get('errors', 0)} wrong words, finding "
+            f"{finding_text(r.get('finding') or {'kind': 'none'})}; {r.get('wall_s', 0):.1f} s")

@@ -33,7 +33,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
-from .native import load_cdll
+from .native import bind_cdll
 
 PARTS = ("walk", "branch")
 # the native op index (IfetchBranchOp of ifetch_ref.h): index into this
@@ -81,15 +81,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_ifetch.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_ifetch.so", _signatures())
     return _lib
 
 
@@ -234,6 +226,19 @@ def ifetch_test(device: int = 0, parts: Sequence[str] = PARTS, nbs: Sequence[int
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    p = r.get("parts") or {}
+    walk, br = p.get("walk") or {}, p.get("branch") or {}
+    rows = walk.get("rows") or {}
+    feet = [v.get("footprint_bytes", 0) for v in rows.values()]
+    span = f"{min(feet) / 1024:.0f}-{max(feet) / 1024:.0f} KiB of code" if feet else "no rows"
+    per = "/".join(f"{v.get('ns_per_block', 0):.0f}" for v in rows.values())
+    return (f"walk {len(rows)} footprints ({span}) x {walk.get('steps', '?')} blocks per wave ({per} ns per block), "
+            f"{len(br.get('ops') or {})} branch ops x {br.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of "
+            f"{r.get('xcds', '?')} XCDs, {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
 
 
 def block_map(device: int = 0) -> List[int]:

@@ -22,7 +22,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native op index (LanesOp of lanes_ref.h): index into this
 OPS = (
@@ -62,15 +62,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_lanes.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_lanes.so", _signatures())
     return _lib
 
 
@@ -146,6 +138,14 @@ def lanes_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = 2000, rep
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows = r.get("ops") or {}
+    rate = sum(v.get("gops", 0) for v in rows.values()) / len(rows) if rows else 0.0
+    return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+            f"XCDs, {r.get('errors', 0)} wrong lanes; {r.get('ms', 0):.1f} ms, mean {rate:.0f} G crossings/s")
 
 
 def apply(op: str, x: Sequence[int], y: Optional[Sequence[int]] = None, iter: int = 0,

@@ -24,7 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary
 from .lanes import simd_name
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native op index (MATRIX_OP_TABLE of matrix_ref.h): index into this
 OPS = (
@@ -83,15 +83,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_matrix.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_matrix.so", _signatures())
     return _lib
 
 
@@ -169,6 +161,13 @@ def matrix_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows = r.get("ops") or {}
+    return (f"{len(rows)} ops x {r.get('iters', '?')} rounds on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} "
+            f"XCDs, {r.get('errors', 0)} wrong elements; {r.get('ms', 0):.1f} ms")
 
 
 def apply(op: str, a: Sequence[int], b: Sequence[int], c: Sequence[int], idx: Optional[Sequence[int]] = None,

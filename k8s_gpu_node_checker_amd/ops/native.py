@@ -82,3 +82,18 @@ def load_cdll(filename: str, required: bool = False) -> "Optional[ctypes.CDLL]":
             f"`python -m k8s_gpu_node_checker_amd.build`")
     _cache[key] = lib
     return lib
+
+
+def bind_cdll(filename: str, signatures: "Dict[str, tuple]") -> "ctypes.CDLL":
+    """The required library ``filename`` with ``signatures`` applied: name -> (argtypes, restype), None leaving
+    ctypes' default (no declared arguments / an int result).  Every name is looked up here, so a library built from
+    an older tree raises AttributeError at load instead of being called with another generation's argument list."""
+    L = load_cdll(filename, required=True)
+    assert L is not None
+    for name, (argtypes, restype) in signatures.items():
+        fn = getattr(L, name)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        if restype is not None:
+            fn.restype = restype
+    return L

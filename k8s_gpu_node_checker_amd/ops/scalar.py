@@ -27,7 +27,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name
-from .native import load_cdll
+from .native import bind_cdll
 
 # the native op index (ScalarOp of scalar_ref.h): index into this
 OPS = (
@@ -92,15 +92,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_scalar.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_scalar.so", _signatures())
     return _lib
 
 
@@ -286,6 +278,22 @@ def scalar_test(device: int = 0, parts: Sequence[str] = PARTS, ops: Sequence[str
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    p = r.get("parts") or {}
+    salu, sgpr, smem = p.get("salu") or {}, p.get("sgpr") or {}, p.get("smem") or {}
+    said = []
+    if salu:
+        said.append(f"{len(salu.get('ops') or {})} ops x {salu.get('iters', '?')} steps {salu.get('errors', 0)} wrong")
+    if sgpr:
+        said.append(f"{sgpr.get('regs_per_wave', '?')} SGPRs x {(sgpr.get('waves_per_simd') or {}).get('max', 0):g} "
+                    f"waves per SIMD {sgpr.get('errors', 0)} wrong")
+    if smem:
+        said.append(f"{len(smem.get('kinds') or {})} load kinds {smem.get('errors', 0)} wrong")
+    return (f"{'; '.join(said) or 'no part'}; {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
+            f"{r.get('ms', 0):.1f} ms")
 
 
 def apply_many(op: str, rows: Sequence[Tuple[int, int, int]], device: int = 0) -> List[Tuple[int, int]]:

@@ -30,7 +30,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary, simd_name
-from .native import load_cdll
+from .native import bind_cdll
 
 ISOLATE_ROW = "isolate/1k"
 FRAMES_ROWS = ("frames/index", "frames/calls")
@@ -66,15 +66,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_scratch.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_scratch.so", _signatures())
     return _lib
 
 
@@ -180,3 +172,11 @@ def scratch_test(device: int = 0, rows: Sequence[str] = ROWS, blocks: Optional[i
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows = r.get("rows") or {}
+    return (f"{len(rows)} rows ({', '.join(rows)}) on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
+            f"{r.get('isolate_waves', '?')} isolate waves x {r.get('rounds', '?')} rounds ({r.get('co_resident_waves', '?')} "
+            f"frames live at once), {r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")

@@ -35,7 +35,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from .diag import simd_map_summary
 from .lanes import simd_name
-from .native import load_cdll
+from .native import bind_cdll
 
 _WIDTHS = ("ubyte", "sbyte", "ushort", "sshort", "dword", "dwordx2", "dwordx3", "dwordx4")
 _STORE_WIDTHS = ("byte", "byte_d16_hi", "short", "short_d16_hi", "dword", "dwordx2", "dwordx3", "dwordx4")
@@ -95,15 +95,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_vmem.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_vmem.so", _signatures())
     return _lib
 
 
@@ -286,6 +278,15 @@ def vmem_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_IT
     if slots:
         res["slots"] = seen
     return res
+
+
+def summary(r: Dict[str, Any]) -> str:
+    """One line of numbers for a result (``diag.render_text``)."""
+    rows, b, l1, dma = r.get("ops") or {}, r.get("bounds") or {}, r.get("l1") or {}, r.get("ldsdma") or {}
+    return (f"{len(rows)} ops x {r.get('iters', '?')} steps on {r.get('simds', '?')} SIMDs of {r.get('xcds', '?')} XCDs, "
+            f"{len(b.get('rows') or {})} bounds rows, L1 {l1.get('slice_bytes', '?')} B x {l1.get('passes', '?')} passes "
+            f"(sc1 / plain {l1.get('l1_gain', 0):.2f}), {len(dma.get('forms') or {})} LDS-DMA forms, "
+            f"{r.get('errors', 0)} wrong words; {r.get('ms', 0):.1f} ms")
 
 
 def apply(op: str, table_words: Sequence[int], offsets: Sequence[int], preset: Optional[Sequence[int]] = None,

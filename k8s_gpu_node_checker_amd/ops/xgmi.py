@@ -14,7 +14,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Tuple
 
-from .native import load_cdll
+from .native import bind_cdll
 
 MODES = ("store", "load")  # the native `mode` argument: index into this
 HUNG = -4                  # xgmi_kernel_fan: the launches (or the verification) missed the deadline
@@ -43,15 +43,7 @@ def _signatures() -> Dict[str, Tuple[Optional[list], Any]]:
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        L = load_cdll("libmi355x_xgmi.so", required=True)
-        assert L is not None
-        for name, (argtypes, restype) in _signatures().items():  # every name is looked up at load
-            fn = getattr(L, name)
-            if argtypes is not None:
-                fn.argtypes = argtypes
-            if restype is not None:
-                fn.restype = restype
-        _lib = L
+        _lib = bind_cdll("libmi355x_xgmi.so", _signatures())
     return _lib
 
 

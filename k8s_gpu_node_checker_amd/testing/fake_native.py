@@ -19,19 +19,29 @@ import time
 from typing import Dict, List, Optional, Tuple
 
 
-def diag_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeDiagLib` stands in for, read from csrc/diag/diag.hip: every function defined at the
-    top level of its ``extern "C"`` blocks -> its parameter declarations (``(void)``: none).  Exports of diagnostic
-    builds only (inside an ``#ifdef``) are left out."""
+def c_exports(name: str, prefix: Optional[str] = None) -> Dict[str, List[str]]:
+    """The C ABI that the stand-in of ``libmi355x_<name>.so`` stands in for, read from csrc/<name>/<name>.hip: every
+    function ``<prefix>...`` (default ``<name>_``) defined at the top level of its ``extern "C"`` blocks -> its parameter
+    declarations (``(void)``: none).  Exports of diagnostic builds only (inside an ``#ifdef``) are left out."""
     import os
     import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "diag", "diag.hip")) as f:
+    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", name, name + ".hip")) as f:
         source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
+    defined = r"^\w[\w ]*[ *]+(%s\w+)\(([^)]*)\)\s*\{" % re.escape(prefix or name + "_")
     out: Dict[str, List[str]] = {}
     for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(diag_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        for fn, params in re.findall(defined, block, re.M):
+            out[fn] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
     return out
+
+
+def __getattr__(attr: str):
+    """``<name>_c_exports()``, the per-library spelling that tests written before :func:`c_exports` import: the same
+    call with the name bound."""
+    if attr.endswith("_c_exports"):
+        import functools
+        return functools.partial(c_exports, attr[:-len("_c_exports")])
+    raise AttributeError(f"module {__name__!r} has no attribute {attr!r}")
 
 
 def _put(ptr, ctype, value) -> None:
@@ -442,20 +452,6 @@ class FakeDiagLib:
         return 0
 
 
-def xgmi_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeXgmiLib` stands in for, read from csrc/xgmi/xgmi.hip the way
-    :func:`diag_c_exports` reads diag.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "xgmi", "xgmi.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(xgmi_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
-
-
 class FakeXgmiLib:
     """``libmi355x_xgmi.so`` for a node of ``n`` GPUs.
 
@@ -514,20 +510,6 @@ class FakeXgmiLib:
         return 0
 
 
-def atomics_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeAtomicsLib` stands in for, read from csrc/atomics/atomics.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "atomics", "atomics.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(atomics_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
-
-
 class FakeAtomicsLib:
     """``libmi355x_atomics.so`` for a node of ``n`` GPUs: every kind clean on all ``xcds`` XCDs.
 
@@ -579,20 +561,6 @@ class FakeAtomicsLib:
             for x in range(8):
                 xcd_waves[8 * k + x] = max(1, -(-words // 64) * adders // self.xcds) if on and x < self.xcds else 0
         return 0
-
-
-def hbmscan_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeHbmscanLib` stands in for, read from csrc/hbmscan/hbmscan.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "hbmscan", "hbmscan.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(hbmscan_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 class FakeHbmscanLib:
@@ -687,20 +655,6 @@ class FakeHbmscanLib:
         return 0
 
 
-def lanes_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeLanesLib` stands in for, read from csrc/lanes/lanes.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "lanes", "lanes.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(lanes_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
-
-
 class FakeLanesLib:
     """``libmi355x_lanes.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD.
 
@@ -771,20 +725,6 @@ class FakeLanesLib:
     def lanes_apply(self, device, op, iter, x_in, y_in, x_out, y_out):
         self.err = b"lanes apply: the stand-in has no wave to apply an instruction on"
         return -1
-
-
-def cvt_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeCvtLib` stands in for, read from csrc/cvt/cvt.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "cvt", "cvt.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(cvt_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 def cvt_c_ops() -> List[str]:
@@ -891,20 +831,6 @@ class FakeCvtLib:
     def cvt_apply_many(self, device, op, rows, nrows, out):
         self.err = b"cvt apply: the stand-in has no wave to apply an instruction on"
         return -1
-
-
-def ifetch_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeIfetchLib` stands in for, read from csrc/ifetch/ifetch.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "ifetch", "ifetch.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(ifetch_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 class FakeIfetchLib:
@@ -1045,20 +971,6 @@ class FakeIfetchLib:
         return -1
 
 
-def handoff_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeHandoffLib` stands in for, read from csrc/handoff/handoff.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "handoff", "handoff.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(handoff_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
-
-
 class FakeHandoffLib:
     """``libmi355x_handoff.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row clean and complete, block b on
     CU ``b // xcds`` of XCD ``b % xcds`` (so ``cross`` pairs lie on different XCDs and ``same`` pairs on one).
@@ -1195,20 +1107,6 @@ class FakeHandoffLib:
                 for j, v in enumerate(gave_up):
                     tmo[4 * k + j] = v
         return 0
-
-
-def scratch_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeScratchLib` stands in for, read from csrc/scratch/scratch.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "scratch", "scratch.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(scratch_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 class FakeScratchLib:
@@ -1349,20 +1247,6 @@ class FakeScratchLib:
         return 0
 
 
-def matrix_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeMatrixLib` stands in for, read from csrc/matrix/matrix.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "matrix", "matrix.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(matrix_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
-
-
 class FakeMatrixLib:
     """``libmi355x_matrix.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD.
 
@@ -1434,20 +1318,6 @@ class FakeMatrixLib:
     def matrix_apply(self, device, op, a, b, c, idx, scale_a, scale_b, d):
         self.err = b"matrix apply: the stand-in has no wave to apply an instruction on"
         return -1
-
-
-def vmem_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeVmemLib` stands in for, read from csrc/vmem/vmem.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "vmem", "vmem.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(vmem_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 class FakeVmemLib:
@@ -1621,20 +1491,6 @@ class FakeVmemLib:
     def vmem_apply(self, device, op, n, mem_words, nwords, offsets, regs, stride, num_records, out):
         self.err = b"vmem apply: the stand-in has no wave to apply an instruction on"
         return -1
-
-
-def scalar_c_exports() -> Dict[str, List[str]]:
-    """The C ABI that :class:`FakeScalarLib` stands in for, read from csrc/scalar/scalar.hip the way
-    :func:`xgmi_c_exports` reads xgmi.hip."""
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(__file__), "..", "csrc", "scalar", "scalar.hip")) as f:
-        source = re.sub(r"^#ifdef .*?^#endif", "", f.read(), flags=re.M | re.S)
-    out: Dict[str, List[str]] = {}
-    for block in re.findall(r'^extern "C" \{$(.*?)^\}  // extern "C"$', source, re.M | re.S):
-        for name, params in re.findall(r"^\w[\w ]*[ *]+(scalar_\w+)\(([^)]*)\)\s*\{", block, re.M):
-            out[name] = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
-    return out
 
 
 _M32, _M64 = 0xffffffff, (1 << 64) - 1

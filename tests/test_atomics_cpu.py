@@ -20,7 +20,7 @@ from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, atomics, diag, fabric
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeAtomicsLib, FakeDiagLib, FakeFabricLib,
-                                                          atomics_c_exports)
+                                                          c_exports)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "atomics")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -30,7 +30,7 @@ HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
 
 def test_exports_match_the_signature_table_and_the_fake():
     import inspect
-    exports, sig = atomics_c_exports(), atomics._signatures()
+    exports, sig = c_exports("atomics"), atomics._signatures()
     assert set(exports) == set(sig) == {"atomics_last_error", "atomics_device_count", "atomics_test"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)
     for name, params in exports.items():

@@ -24,7 +24,7 @@ from k8s_gpu_node_checker_amd.agent import node_cycle
 from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, cvt, diag, fabric
 from k8s_gpu_node_checker_amd.testing import fixtures
-from k8s_gpu_node_checker_amd.testing.fake_native import FakeCvtLib, FakeDiagLib, FakeFabricLib, cvt_c_exports, cvt_c_ops
+from k8s_gpu_node_checker_amd.testing.fake_native import FakeCvtLib, FakeDiagLib, FakeFabricLib, c_exports, cvt_c_ops
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "cvt")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -717,7 +717,7 @@ def test_the_reference_is_clean_under_the_host_sanitizers():
 # --- ABI -------------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = cvt_c_exports(), cvt._signatures()
+    exports, sig = c_exports("cvt"), cvt._signatures()
     assert set(exports) == set(sig) == {"cvt_last_error", "cvt_device_count", "cvt_slots", "cvt_ops", "cvt_row_words", "cvt_shape_rows",
                                         "cvt_model_rows", "cvt_test", "cvt_apply_many"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)

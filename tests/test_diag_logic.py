@@ -470,12 +470,12 @@ def test_fake_abi_has_every_entry_point_the_front_end_calls_with_the_c_arity():
     import inspect
     import re
 
-    from k8s_gpu_node_checker_amd.testing.fake_native import diag_c_exports
+    from k8s_gpu_node_checker_amd.testing.fake_native import c_exports
     with open(diag.__file__) as f:
         source = f.read()
     # read as attributes of lib(), or named in a string: the signature table, getattr() and the shared helpers' ``fn``
     used = set(re.findall(r"(?:\bL|lib\(\))\.(diag_\w+)", source)) | set(re.findall(r"\"(diag_\w+)\"", source))
-    exports = diag_c_exports()
+    exports = c_exports("diag")
     assert {"diag_gemm_bf16", "diag_valu_burn", "diag_p2p_fan", "diag_last_error"} <= used  # the scan finds them
     assert used <= set(exports), used - set(exports)
     faked = {n for n in vars(FakeDiagLib) if n.startswith("diag_")}

@@ -23,7 +23,7 @@ from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, handoff, lanes
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeDiagLib, FakeFabricLib, FakeHandoffLib, FakeLanesLib,
-                                                          handoff_c_exports)
+                                                          c_exports)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "handoff")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -170,7 +170,7 @@ def test_the_classifier_on_hand_made_rows():
 # --- 3. ABI ----------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = handoff_c_exports(), handoff._signatures()
+    exports, sig = c_exports("handoff"), handoff._signatures()
     assert set(exports) == set(sig) == {"handoff_last_error", "handoff_device_count", "handoff_slots", "handoff_lds_bytes",
                                         "handoff_test"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)

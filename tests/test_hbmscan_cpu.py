@@ -20,7 +20,7 @@ from k8s_gpu_node_checker_amd.agent import node_cycle
 from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, hbmscan
 from k8s_gpu_node_checker_amd.testing import fixtures
-from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeHbmscanLib, hbmscan_c_exports
+from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeHbmscanLib, c_exports
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "hbmscan")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -327,7 +327,7 @@ def test_classify_names_each_of_the_five_findings(sanitize):
 
 def test_exports_match_the_signature_table_and_the_fake():
     import inspect
-    exports, sig = hbmscan_c_exports(), hbmscan._signatures()
+    exports, sig = c_exports("hbmscan"), hbmscan._signatures()
     assert set(exports) == set(sig) == EXPORTS
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)
     for name, params in exports.items():

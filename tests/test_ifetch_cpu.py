@@ -21,7 +21,7 @@ from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, ifetch, lanes
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeDiagLib, FakeFabricLib, FakeIfetchLib, FakeLanesLib,
-                                                          ifetch_c_exports)
+                                                          c_exports)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "ifetch")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -297,7 +297,7 @@ def test_every_branch_op_is_the_independent_select():
 
 def test_exports_match_the_signature_table_and_the_fake():
     import inspect
-    exports, sig = ifetch_c_exports(), ifetch._signatures()
+    exports, sig = c_exports("ifetch"), ifetch._signatures()
     assert set(exports) == set(sig) == {"ifetch_last_error", "ifetch_device_count", "ifetch_slots", "ifetch_blocks",
                                         "ifetch_block_map", "ifetch_walk_test", "ifetch_branch_test",
                                         "ifetch_apply_blocks", "ifetch_apply"}

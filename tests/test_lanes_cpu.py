@@ -21,7 +21,7 @@ from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, atomics, diag, fabric, lanes
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeAtomicsLib, FakeDiagLib, FakeFabricLib, FakeLanesLib,
-                                                          lanes_c_exports)
+                                                          c_exports)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "lanes")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -233,7 +233,7 @@ def test_the_reference_is_clean_under_the_host_sanitizers():
 
 def test_exports_match_the_signature_table_and_the_fake():
     import inspect
-    exports, sig = lanes_c_exports(), lanes._signatures()
+    exports, sig = c_exports("lanes"), lanes._signatures()
     assert set(exports) == set(sig) == {"lanes_last_error", "lanes_device_count", "lanes_slots", "lanes_test",
                                         "lanes_apply"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)

@@ -22,7 +22,7 @@ from k8s_gpu_node_checker_amd.agent import node_cycle
 from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, matrix
 from k8s_gpu_node_checker_amd.testing import fixtures
-from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeMatrixLib, matrix_c_exports
+from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeMatrixLib, c_exports
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "matrix")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -331,7 +331,7 @@ def test_the_reference_is_clean_under_the_host_sanitizers():
 # --- ABI -------------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = matrix_c_exports(), matrix._signatures()
+    exports, sig = c_exports("matrix"), matrix._signatures()
     assert set(exports) == set(sig) == {"matrix_last_error", "matrix_device_count", "matrix_slots", "matrix_test",
                                         "matrix_apply"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)

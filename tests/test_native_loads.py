@@ -106,13 +106,13 @@ def test_diag_exports_match_their_ctypes_signatures(monkeypatch):
     import os
 
     from k8s_gpu_node_checker_amd.ops import diag, native
-    from k8s_gpu_node_checker_amd.testing.fake_native import diag_c_exports
+    from k8s_gpu_node_checker_amd.testing.fake_native import c_exports
     if not os.path.exists(os.path.join(native.NATIVE_DIR, "libmi355x_diag.so")):
         pytest.skip("libmi355x_diag.so not built (no hipcc)")
     monkeypatch.setattr(diag, "_lib", None)  # the real library, whatever another test installed
     L = diag.lib()
     assert isinstance(L, ctypes.CDLL)
-    exports = diag_c_exports()
+    exports = c_exports("diag")
     assert len(DIAG_EXPORTS) == 38 and set(exports) == DIAG_EXPORTS, sorted(set(exports) ^ DIAG_EXPORTS)
     for name, params in exports.items():
         fn = getattr(L, name)  # AttributeError: not exported

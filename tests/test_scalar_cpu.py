@@ -23,7 +23,7 @@ from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, atomics, diag, fabric, lanes, scalar
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeAtomicsLib, FakeDiagLib, FakeFabricLib, FakeLanesLib,
-                                                          FakeScalarLib, scalar_c_exports, scalar_model)
+                                                          FakeScalarLib, c_exports, scalar_model)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "scalar")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -440,7 +440,7 @@ def test_the_reference_is_clean_under_the_host_sanitizers():
 # --- 2. ABI ----------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = scalar_c_exports(), scalar._signatures()
+    exports, sig = c_exports("scalar"), scalar._signatures()
     assert set(exports) == set(sig) == {"scalar_last_error", "scalar_device_count", "scalar_slots", "scalar_sgpr_lo",
                                         "scalar_sgpr_hi", "scalar_sgpr_regs", "scalar_salu", "scalar_sgpr",
                                         "scalar_smem", "scalar_apply"}

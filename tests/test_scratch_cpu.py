@@ -22,7 +22,7 @@ from k8s_gpu_node_checker_amd.agent import node_cycle
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, lanes, scratch
 from k8s_gpu_node_checker_amd.testing import fixtures
 from k8s_gpu_node_checker_amd.testing.fake_native import (FakeDiagLib, FakeFabricLib, FakeLanesLib, FakeScratchLib,
-                                                          scratch_c_exports)
+                                                          c_exports)
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "scratch")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -224,7 +224,7 @@ def test_the_frames_routines_are_the_independent_ones():
 # --- 3. ABI ----------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = scratch_c_exports(), scratch._signatures()
+    exports, sig = c_exports("scratch"), scratch._signatures()
     assert set(exports) == set(sig) == {"scratch_last_error", "scratch_device_count", "scratch_slots", "scratch_rows",
                                         "scratch_test"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)

@@ -22,7 +22,7 @@ from k8s_gpu_node_checker_amd.agent import node_cycle
 from k8s_gpu_node_checker_amd.models import health as H
 from k8s_gpu_node_checker_amd.ops import amdsmi_probe, diag, fabric, vmem
 from k8s_gpu_node_checker_amd.testing import fixtures
-from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeVmemLib, vmem_c_exports
+from k8s_gpu_node_checker_amd.testing.fake_native import FakeDiagLib, FakeFabricLib, FakeVmemLib, c_exports
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "vmem")
 HIPCC = os.path.join(B.ROCM, "bin", "hipcc")
@@ -271,7 +271,7 @@ def test_the_reference_is_clean_under_the_host_sanitizers():
 # --- ABI -------------------------------------------------------------------------------------------------------
 
 def test_exports_match_the_signature_table_and_the_fake():
-    exports, sig = vmem_c_exports(), vmem._signatures()
+    exports, sig = c_exports("vmem"), vmem._signatures()
     assert set(exports) == set(sig) == {"vmem_last_error", "vmem_device_count", "vmem_slots", "vmem_ops", "vmem_loads",
                                         "vmem_walk_reads", "vmem_walks", "vmem_bounds", "vmem_l1", "vmem_ldsdma_forms",
                                         "vmem_ldsdma_name", "vmem_ldsdma", "vmem_apply"}

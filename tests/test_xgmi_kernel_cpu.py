@@ -32,8 +32,8 @@ def fakes(monkeypatch):
 
 def test_xgmi_exports_match_the_signature_table():
     from k8s_gpu_node_checker_amd.ops import xgmi
-    from k8s_gpu_node_checker_amd.testing.fake_native import xgmi_c_exports
-    exports, sig = xgmi_c_exports(), xgmi._signatures()
+    from k8s_gpu_node_checker_amd.testing.fake_native import c_exports
+    exports, sig = c_exports("xgmi"), xgmi._signatures()
     assert set(exports) == set(sig) == {"xgmi_last_error", "xgmi_device_count", "xgmi_kernel_fan"}
     pointers = (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)
     for name, params in exports.items():
