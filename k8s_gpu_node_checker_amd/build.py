@@ -15,7 +15,8 @@ artefact               source                                              toolc
 =====================  ==================================================  ==========================
 
 The HIP libraries share ``csrc/common/hip_host.h`` (one build line for all; includes are relative, no ``-I``);
-{simd_located} also share ``csrc/common/simd_report.h``.
+{simd_located} also share ``csrc/common/simd_report.h``, and the instruction-level ones among them
+``csrc/common/op_list.h``.
 The opt-in diagnostics' targets and their rows above are generated from ``ops/optin.OPT_IN``.
 Every header a source reaches is listed in its target's ``headers``, so a change to one rebuilds the library.
 The ifetch library's one large kernel (more than 400 KiB of code) takes about 40 s to compile, the longest of all.
@@ -58,6 +59,8 @@ def _targets() -> Dict[str, Dict[str, object]]:
     hip_cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-result"]
     hip_host = os.path.join(CSRC, "common", "hip_host.h")  # the host helpers every HIP library shares
     simd_report = os.path.join(CSRC, "common", "simd_report.h")  # the report of the SIMD-located diagnostics
+    op_list = os.path.join(CSRC, "common", "op_list.h")  # the op-list and self-check hook decisions ...
+    op_list_users = ("lanes", "scalar", "matrix", "vmem", "cvt", "ifetch")  # ... of the instruction-level diagnostics
     return {
         "fastpath": {
             "sources": [os.path.join(CSRC, "fastpath", "fastpath.cpp")],
@@ -102,7 +105,7 @@ def _targets() -> Dict[str, Dict[str, object]]:
         **{name: {  # the opt-in diagnostics (ops/optin.py), one library each
             "sources": [os.path.join(CSRC, name, f"{name}.hip")],
             "headers": [os.path.join(CSRC, name, f"{name}_ref.h"), hip_host]
-            + ([simd_report] if entry.simd_report else []),
+            + ([simd_report] if entry.simd_report else []) + ([op_list] if name in op_list_users else []),
             "out": os.path.join(OUT, f"libmi355x_{name}.so"),
             "cmd": hip_cmd,
             "requires": hipcc,

@@ -58,6 +58,11 @@ inline int refuse_memory(const char* prefix, const std::string& what, const hipF
   return -3;
 }
 
+// the grid of an entry point: `blocks` workgroups as asked for, or (0) `per_cu` for every CU of `device`
+inline unsigned default_grid(int device, int blocks, int per_cu) {
+  return blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * per_cu;
+}
+
 // the report and the map of one entry point, and its checked, timed launches
 struct Run {
   static constexpr size_t MAP_BYTES = static_cast<size_t>(SIMD_ROWS) * SIMD_MAP_COLS * sizeof(unsigned long long);
@@ -100,6 +105,25 @@ struct Run {
     if (const int rc = clear()) return rc;
     if (const int rc = launch(enqueue, ms)) return rc;
     return collect(errors, rec);
+  }
+  // The usual series: launch r = 0, the warm-up (which carries the self-check hooks), then `reps` timed launches, each
+  // of what enqueue(r) queues and each checked(); *mean_ms = the mean time of the timed ones.  after(r) runs once
+  // launch r has been collected.  Ends at the first non-zero code, of a launch or of after(), and returns it.
+  template <typename F, typename A>
+  int series(int reps, F&& enqueue, unsigned long long* errors, unsigned long long* rec, double* mean_ms, A&& after) {
+    double total_ms = 0.0;
+    for (int r = 0; r <= reps; ++r) {
+      float t = 0.f;
+      if (const int rc = checked([&] { enqueue(r); }, &t, errors, rec)) return rc;
+      if (const int rc = after(r)) return rc;
+      if (r > 0) total_ms += t;
+    }
+    *mean_ms = total_ms / reps;
+    return 0;
+  }
+  template <typename F>
+  int series(int reps, F&& enqueue, unsigned long long* errors, unsigned long long* rec, double* mean_ms) {
+    return series(reps, enqueue, errors, rec, mean_ms, [](int) { return 0; });
   }
   int read_map(unsigned long long* simd_map) {
     HIP_CHECK(hipMemcpy(simd_map, dmap.ptr, MAP_BYTES, hipMemcpyDeviceToHost));

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "cvt_ref.h"
 
@@ -470,29 +471,22 @@ int cvt_test(int device, int blocks, int iters, int reps, const int* ops, int no
              int inject_skip_iter, unsigned long long* errors, unsigned long long* first, double* ms, unsigned int* mode,
              unsigned long long* simd_map, int* blocks_run) {
   const int n = device_count();
-  bool known = ops != nullptr && nops >= 1 && nops <= CVT_OPS, hook_listed = inject_op < 0;
-  bool seen[CVT_OPS] = {};
-  for (int i = 0; known && i < nops; ++i) {
-    known = ops[i] >= 0 && ops[i] < CVT_OPS && !seen[ops[i]];
-    if (known) seen[ops[i]] = true;
-    hook_listed = hook_listed || ops[i] == inject_op;
-  }
-  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 || !known) {
+  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 ||
+      !op_list_known(ops, nops, CVT_OPS, true)) {
     g_err = "cvt test: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^16, reps >= 1 and a list of distinct known ops";
     return -2;
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (!hook_listed || (inject_op >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid || inject_skip_iter >= iters))) {
+  if (!op_list_has_hook(ops, nops, inject_op) || (inject_op >= 0 && !hook_in_range(inject_block, grid, inject_skip_iter, iters))) {
     g_err = "cvt test: inject_op must be in the list, inject_block inside the grid and inject_skip_iter below iters";
     return -2;
   }
   for (int k = 0; k < CVT_OPS; ++k) {
     errors[k] = 0;
-    first[4 * k] = ~0ULL;
-    first[4 * k + 1] = first[4 * k + 2] = first[4 * k + 3] = 0;
+    no_record(first + 4 * k);
     ms[k] = 0.0;
   }
   *mode = 0;
@@ -513,29 +507,25 @@ int cvt_test(int device, int blocks, int iters, int reps, const int* ops, int no
       return -3;
     }
     HIP_CHECK(hipMemcpy(dexp.ptr, expect.data(), expect.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    double total_ms = 0.0;
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
-      const Launch l = {static_cast<const uint32_t*>(dexp.ptr), cvt_op_seed(seed, k), iters,
-                        hooked && inject_skip_iter < 0 ? inject_block : -1,
-                        hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
-                        run.rep(), run.map(), static_cast<uint32_t*>(dmode.ptr), grid};
-      float t = 0.f;
-      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, first + 4 * k)) return rc;
-      if (i == 0 && r == 0) {  // the mode of the first warm-up: nothing is judged under another
-        uint32_t m = 0;
-        HIP_CHECK(hipMemcpy(&m, dmode.ptr, sizeof m, hipMemcpyDeviceToHost));
-        *mode = m;
-        if ((m & 0xffu) != MODE_WANT) {
-          g_err = std::string("cvt test: the waves run with MODE.") + ((m & 0xfu) ? "FP_ROUND" : "FP_DENORM") + " = " +
-                  std::to_string((m & 0xfu) ? (m & 0xfu) : ((m >> 4) & 0xfu)) +
-                  ": the model holds for round-to-nearest-even (0) with denormals kept (15)";
-          return -3;
-        }
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_iter);
+      AllOps::launch[k]({static_cast<const uint32_t*>(dexp.ptr), cvt_op_seed(seed, k), iters, h.flip_block, h.skip_block,
+                         h.skip_at, run.rep(), run.map(), static_cast<uint32_t*>(dmode.ptr), grid});
+    };
+    const auto judge_mode = [&](int r) {  // the mode of the first warm-up: nothing is judged under another
+      if (i != 0 || r != 0) return 0;
+      uint32_t m = 0;
+      HIP_CHECK(hipMemcpy(&m, dmode.ptr, sizeof m, hipMemcpyDeviceToHost));
+      *mode = m;
+      if ((m & 0xffu) != MODE_WANT) {
+        g_err = std::string("cvt test: the waves run with MODE.") + ((m & 0xfu) ? "FP_ROUND" : "FP_DENORM") + " = " +
+                std::to_string((m & 0xfu) ? (m & 0xfu) : ((m >> 4) & 0xfu)) +
+                ": the model holds for round-to-nearest-even (0) with denormals kept (15)";
+        return -3;
       }
-      if (r > 0) total_ms += t;
-    }
-    ms[k] = total_ms / reps;
+      return 0;
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, first + 4 * k, ms + k, judge_mode)) return rc;
   }
   return run.read_map(simd_map);
 }

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "ifetch_ref.h"
 
@@ -421,16 +422,15 @@ int ifetch_walk_test(int device, int blocks, int steps, int reps, const int* nbs
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (inject_row >= 0 && (inject_row >= nrows || inject_block < 0 || static_cast<unsigned>(inject_block) >= grid ||
-                          inject_skip_step >= steps)) {
+  if (inject_row >= 0 && (inject_row >= nrows || !hook_in_range(inject_block, grid, inject_skip_step, steps))) {
     g_err = "ifetch walk: inject_row must be one of the rows, inject_block inside the grid and inject_skip_step below steps";
     return -2;
   }
   for (int k = 0; k < nrows; ++k) {
     errors[k] = footprint[k] = 0;
-    first[4 * k] = ~0ULL, first[4 * k + 1] = first[4 * k + 2] = first[4 * k + 3] = 0;
+    no_record(first + 4 * k);
     ms[k] = 0.0;
     visited[k] = 0;
   }
@@ -455,23 +455,13 @@ int ifetch_walk_test(int device, int blocks, int steps, int reps, const int* nbs
   for (int k = 0; k < nrows; ++k) {
     footprint[k] = span[nbs[k] - 1];
     HIP_CHECK(hipMemcpy(dexp.ptr, tables[k].data(), IFETCH_TABLE_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
-    double total_ms = 0.0;
-    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_row;
-      const int flip = hooked && inject_skip_step < 0 ? inject_block : -1;
-      const int skip = hooked && inject_skip_step >= 0 ? inject_block : -1;
-      const auto enqueue = [&] {
-        hipLaunchKernelGGL(walk_kernel, dim3(grid), dim3(THREADS), 0, nullptr, static_cast<const uint32_t*>(dexp.ptr),
-                           nullptr, 0, nullptr, nullptr, nullptr, seed, steps, static_cast<uint32_t>(nbs[k]), flip, skip,
-                           hooked ? inject_skip_step : -1, run.rep(), run.map());
-      };
-      float t = 0.f;
-      if (const int rc = run.checked(enqueue, &t, errors + k, rec)) return rc;
-      if (r > 0) total_ms += t;
-    }
-    for (int j = 0; j < 4; ++j) first[4 * k + j] = rec[j];
-    ms[k] = total_ms / reps;
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_row, inject_block, inject_skip_step);
+      hipLaunchKernelGGL(walk_kernel, dim3(grid), dim3(THREADS), 0, nullptr, static_cast<const uint32_t*>(dexp.ptr),
+                         nullptr, 0, nullptr, nullptr, nullptr, seed, steps, static_cast<uint32_t>(nbs[k]), h.flip_block,
+                         h.skip_block, h.skip_at, run.rep(), run.map());
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, first + 4 * k, ms + k)) return rc;
   }
   return run.read_map(simd_map);
 }
@@ -494,27 +484,22 @@ int ifetch_branch_test(int device, int blocks, int iters, int reps, const int* o
                        int inject_block, int inject_skip_iter, unsigned long long* errors, unsigned long long* first,
                        double* ms, unsigned long long* simd_map, int* blocks_run) {
   const int n = device_count();
-  bool known = ops != nullptr && nops >= 1 && nops <= IFETCH_BRANCH_OPS, hook_listed = inject_op < 0;
-  for (int i = 0; known && i < nops; ++i) {
-    known = ops[i] >= 0 && ops[i] < IFETCH_BRANCH_OPS;
-    hook_listed = hook_listed || ops[i] == inject_op;
-  }
-  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 || !known) {
+  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 ||
+      !op_list_known(ops, nops, IFETCH_BRANCH_OPS, false)) {
     g_err = "ifetch branch: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a list of known ops";
     return -2;
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (!hook_listed || (inject_op >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid ||
-                                          inject_skip_iter >= iters))) {
+  if (!op_list_has_hook(ops, nops, inject_op) || (inject_op >= 0 && !hook_in_range(inject_block, grid, inject_skip_iter, iters))) {
     g_err = "ifetch branch: inject_op must be in the list, inject_block inside the grid and inject_skip_iter below iters";
     return -2;
   }
   for (int k = 0; k < IFETCH_BRANCH_OPS; ++k) {
     errors[k] = 0;
-    first[4 * k] = ~0ULL, first[4 * k + 1] = first[4 * k + 2] = first[4 * k + 3] = 0;
+    no_record(first + 4 * k);
     ms[k] = 0.0;
   }
   Run run;
@@ -529,20 +514,14 @@ int ifetch_branch_test(int device, int blocks, int iters, int reps, const int* o
     if (const int rc = refuse("ifetch branch", attr, IFETCH_BRANCH_TABLE[k].name)) return rc;
     ifetch_branch_expected(k, ifetch_op_seed(seed, k), iters, -1, expect);
     HIP_CHECK(hipMemcpy(dexp.ptr, expect, sizeof expect, hipMemcpyHostToDevice));
-    double total_ms = 0.0;
-    unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
-      const BranchLaunch l = {static_cast<const uint32_t*>(dexp.ptr), ifetch_op_seed(seed, k), iters,
-                              hooked && inject_skip_iter < 0 ? inject_block : -1,
-                              hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
-                              run.rep(), run.map(), grid};
-      float t = 0.f;
-      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
-      if (r > 0) total_ms += t;
-    }
+    unsigned long long rec[4] = {~0ULL, 0, 0, 0};  // of this series: an op listed twice reports its last one's
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_iter);
+      AllOps::launch[k]({static_cast<const uint32_t*>(dexp.ptr), ifetch_op_seed(seed, k), iters, h.flip_block, h.skip_block,
+                         h.skip_at, run.rep(), run.map(), grid});
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, rec, ms + k)) return rc;
     for (int j = 0; j < 4; ++j) first[4 * k + j] = rec[j];
-    ms[k] = total_ms / reps;
   }
   return run.read_map(simd_map);
 }

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "lanes_ref.h"
 
@@ -195,10 +196,10 @@ int lanes_test(int device, int blocks, int iters, int reps, unsigned long long o
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (inject_op >= 0 && (inject_op >= LANES_OPS || !((op_mask >> inject_op) & 1ULL) || inject_block < 0 ||
-                         static_cast<unsigned>(inject_block) >= grid || inject_skip_iter >= iters)) {
+  if (inject_op >= 0 && (inject_op >= LANES_OPS || !((op_mask >> inject_op) & 1ULL) ||
+                         !hook_in_range(inject_block, grid, inject_skip_iter, iters))) {
     g_err = "lanes test: inject_op must be in the mask, inject_block inside the grid and inject_skip_iter below iters";
     return -2;
   }
@@ -220,20 +221,14 @@ int lanes_test(int device, int blocks, int iters, int reps, unsigned long long o
       return rc;
     lanes_expected(k, seed, iters, -1, expect.data());
     HIP_CHECK(hipMemcpy(dexp.ptr, expect.data(), expect.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    double total_ms = 0.0;
     unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
-      const Launch l = {static_cast<const uint32_t*>(dexp.ptr), lanes_op_seed(seed, k), iters,
-                        hooked && inject_skip_iter < 0 ? inject_block : -1,
-                        hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
-                        run.rep(), run.map(), grid};
-      float t = 0.f;
-      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
-      if (r > 0) total_ms += t;
-    }
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_iter);
+      AllOps::launch[k]({static_cast<const uint32_t*>(dexp.ptr), lanes_op_seed(seed, k), iters, h.flip_block, h.skip_block,
+                         h.skip_at, run.rep(), run.map(), grid});
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, rec, ms + k)) return rc;
     first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
-    ms[k] = total_ms / reps;
   }
   return run.read_map(simd_map);
 }

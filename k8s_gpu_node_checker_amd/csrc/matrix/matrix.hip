@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "matrix_ref.h"
 
@@ -342,24 +343,18 @@ int matrix_test(int device, int blocks, int iters, int reps, const int* ops, int
                 unsigned long long* got, unsigned long long* want, double* ms, unsigned long long* simd_map,
                 int* blocks_run) {
   const int n = device_count();
-  bool ok = device >= 0 && device < n && blocks >= 0 && iters >= 1 && iters <= MAX_ITERS && reps >= 1 && n_ops >= 1 &&
-            n_ops <= MATRIX_OPS;
-  std::vector<char> chosen(MATRIX_OPS, 0);
-  for (int i = 0; ok && i < n_ops; ++i) {
-    ok = ops[i] >= 0 && ops[i] < MATRIX_OPS && !chosen[ops[i]];
-    if (ok) chosen[ops[i]] = 1;
-  }
-  if (!ok) {
+  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 ||
+      !op_list_known(ops, n_ops, MATRIX_OPS, true)) {
     g_err = "matrix test: need a valid device, blocks >= 0 (0: 2 per CU), iters 1..2^20, reps >= 1 and a list of "
             "distinct known ops";
     return -2;
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (inject_op >= 0 && (inject_op >= MATRIX_OPS || !chosen[inject_op] || inject_block < 0 ||
-                         static_cast<unsigned>(inject_block) >= grid || inject_skip_step >= MATRIX_STEPS)) {
+  if (!op_list_has_hook(ops, n_ops, inject_op) ||
+      (inject_op >= 0 && !hook_in_range(inject_block, grid, inject_skip_step, MATRIX_STEPS))) {
     g_err = "matrix test: inject_op must be among the ops, inject_block inside the grid and inject_skip_step below 4";
     return -2;
   }
@@ -386,20 +381,14 @@ int matrix_test(int device, int blocks, int iters, int reps, const int* ops, int
       return -2;
     }
     HIP_CHECK(hipMemcpy(din.ptr, host.data(), sizeof(MatrixOperands), hipMemcpyHostToDevice));
-    double total_ms = 0.0;
     unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
-      const Launch l = {static_cast<const MatrixOperands*>(din.ptr), iters,
-                        hooked && inject_skip_step < 0 ? inject_block : -1,
-                        hooked && inject_skip_step >= 0 ? inject_block : -1, hooked ? inject_skip_step : -1,
-                        run.rep(), run.map(), grid};
-      float t = 0.f;
-      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
-      if (r > 0) total_ms += t;
-    }
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_step);
+      AllOps::launch[k]({static_cast<const MatrixOperands*>(din.ptr), iters, h.flip_block, h.skip_block, h.skip_at, run.rep(),
+                         run.map(), grid});
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, rec, ms + k)) return rc;
     first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
-    ms[k] = total_ms / reps;
   }
   return run.read_map(simd_map);
 }

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "scalar_ref.h"
 
@@ -396,21 +397,16 @@ int scalar_salu(int device, int blocks, int iters, int reps, const int* ops, int
                 unsigned long long* got, unsigned long long* want, double* ms, unsigned long long* simd_map,
                 int* blocks_run) {
   const int n = device_count();
-  bool known = ops != nullptr && nops >= 1 && nops <= SCALAR_OPS, hook_listed = inject_op < 0;
-  for (int i = 0; known && i < nops; ++i) {
-    known = ops[i] >= 0 && ops[i] < SCALAR_OPS;
-    hook_listed = hook_listed || ops[i] == inject_op;
-  }
-  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 || !known) {
+  if (device < 0 || device >= n || blocks < 0 || iters < 1 || iters > MAX_ITERS || reps < 1 ||
+      !op_list_known(ops, nops, SCALAR_OPS, false)) {
     g_err = "scalar salu: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a list of known ops";
     return -2;
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SALU_BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, SALU_BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (!hook_listed || (inject_op >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid ||
-                                          inject_skip_iter >= iters))) {
+  if (!op_list_has_hook(ops, nops, inject_op) || (inject_op >= 0 && !hook_in_range(inject_block, grid, inject_skip_iter, iters))) {
     g_err = "scalar salu: inject_op must be in the list, inject_block inside the grid and inject_skip_iter below iters";
     return -2;
   }
@@ -431,20 +427,14 @@ int scalar_salu(int device, int blocks, int iters, int reps, const int* ops, int
     if (const int rc = refuse(attr, SCALAR_OP_TABLE[k].name)) return rc;
     scalar_expected(k, seed, iters, -1, expect);
     HIP_CHECK(hipMemcpy(dexp.ptr, expect, sizeof expect, hipMemcpyHostToDevice));
-    double total_ms = 0.0;
     unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-    for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
-      const SaluLaunch l = {static_cast<const uint32_t*>(dexp.ptr), scalar_op_seed(seed, k), iters,
-                            hooked && inject_skip_iter < 0 ? inject_block : -1,
-                            hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
-                            run.rep(), run.map(), grid};
-      float t = 0.f;
-      if (const int rc = run.checked([&] { AllOps::launch[k](l); }, &t, errors + k, rec)) return rc;
-      if (r > 0) total_ms += t;
-    }
+    const auto enqueue = [&](int r) {
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_iter);
+      AllOps::launch[k]({static_cast<const uint32_t*>(dexp.ptr), scalar_op_seed(seed, k), iters, h.flip_block, h.skip_block,
+                         h.skip_at, run.rep(), run.map(), grid});
+    };
+    if (const int rc = run.series(reps, enqueue, errors + k, rec, ms + k)) return rc;
     first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
-    ms[k] = total_ms / reps;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
   return 0;
@@ -469,7 +459,7 @@ int scalar_sgpr(int device, int blocks, int reps, int hold, uint64_t seed, int i
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SGPR_BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, SGPR_BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
   if (inject_reg >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid)) {
     g_err = "scalar sgpr: inject_block outside the grid";
@@ -483,19 +473,13 @@ int scalar_sgpr(int device, int blocks, int reps, int hold, uint64_t seed, int i
   if (const int rc = refuse(attr, "the SGPR file")) return rc;
   Run run;
   if (const int rc = run.open(device)) return rc;
-  double total_ms = 0.0;
   unsigned long long rec[4] = {~0ULL, 0, 0, 0};
-  for (int r = 0; r <= reps; ++r) {
-    float t = 0.f;
-    const auto enqueue = [&] {
-      hipLaunchKernelGGL(sgpr_kernel, dim3(grid), dim3(THREADS), 0, nullptr, seed + static_cast<uint64_t>(r), hold,
-                         r == 0 ? inject_block : -1, r == 0 ? inject_reg : -1, run.rep(), run.map());
-    };
-    if (const int rc = run.checked(enqueue, &t, errors, rec)) return rc;
-    if (r > 0) total_ms += t;
-  }
+  const auto enqueue = [&](int r) {
+    hipLaunchKernelGGL(sgpr_kernel, dim3(grid), dim3(THREADS), 0, nullptr, seed + static_cast<uint64_t>(r), hold,
+                       r == 0 ? inject_block : -1, r == 0 ? inject_reg : -1, run.rep(), run.map());
+  };
+  if (const int rc = run.series(reps, enqueue, errors, rec, ms)) return rc;
   *first_where = rec[0], *got = rec[2], *want = rec[3];
-  *ms = total_ms / reps;
   if (const int rc = run.read_map(simd_map)) return rc;
   return 0;
 }
@@ -525,7 +509,7 @@ int scalar_smem(int device, int blocks, int reps, unsigned int small_bytes, unsi
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * SMEM_BLOCKS_PER_CU;
+  const unsigned grid = default_grid(device, blocks, SMEM_BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
   for (int k = 0; k < SCALAR_SMEM_KINDS; ++k) {
     errors[k] = got[k] = want[k] = 0;
@@ -555,13 +539,8 @@ int scalar_smem(int device, int blocks, int reps, unsigned int small_bytes, unsi
     for (int t = 0; t < 2; ++t) {
       const uint32_t nloads = t == 0 ? static_cast<uint32_t>(passes) * (words[0] / width) : static_cast<uint32_t>(loads);
       const SmemLaunch l = {static_cast<const uint32_t*>(table[t].ptr), words[t], seed32, nloads, t, run.rep(), run.map(), grid};
-      double total_ms = 0.0;
-      for (int r = 0; r <= reps; ++r) {
-        float ms = 0.f;
-        if (const int rc = run.checked([&] { AllKinds::launch[k](l); }, &ms, errors + k, rec)) return rc;
-        if (r > 0) total_ms += ms;
-      }
-      (t == 0 ? ms_hit : ms_miss)[k] = total_ms / reps;
+      if (const int rc = run.series(reps, [&](int) { AllKinds::launch[k](l); }, errors + k, rec, (t == 0 ? ms_hit : ms_miss) + k))
+        return rc;
     }
     first_where[k] = rec[0], got[k] = rec[2], want[k] = rec[3];
   }

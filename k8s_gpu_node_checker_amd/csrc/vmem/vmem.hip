@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../common/hip_host.h"
+#include "../common/op_list.h"
 #include "../common/simd_report.h"
 #include "vmem_ref.h"
 
@@ -526,10 +527,6 @@ int refuse(const hipFuncAttributes& attr, const std::string& what, size_t lds_al
                        lds_allowed);
 }
 
-unsigned grid_of(int device, int blocks) {
-  return blocks ? static_cast<unsigned>(blocks) : static_cast<unsigned>(cu_count(device)) * BLOCKS_PER_CU;
-}
-
 void fill_table(std::vector<uint32_t>* t, uint32_t seed) {
   t->resize(VMEM_TABLE_BYTES / 4);
   for (uint32_t i = 0; i < VMEM_TABLE_BYTES / 4; ++i) (*t)[i] = vmem_word(i, seed);
@@ -587,23 +584,17 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
                int inject_block, int inject_skip_iter, long long inject_table_word, unsigned long long* errors,
                unsigned long long* first, double* ms, unsigned long long* simd_map, int* blocks_run) {
   const int n = device_count();
-  bool known = ops != nullptr && nops >= 1 && nops <= VMEM_OPS, hook_listed = inject_op < 0;
-  bool seen[VMEM_OPS] = {};
-  for (int i = 0; known && i < nops; ++i) {
-    known = ops[i] >= 0 && ops[i] < VMEM_OPS && !seen[ops[i]];
-    if (known) seen[ops[i]] = true;
-    hook_listed = hook_listed || ops[i] == inject_op;
-  }
-  if (device < 0 || device >= n || blocks < 0 || blocks > MAX_BLOCKS || iters < 1 || iters > MAX_ITERS || reps < 1 || !known) {
+  if (device < 0 || device >= n || blocks < 0 || blocks > MAX_BLOCKS || iters < 1 || iters > MAX_ITERS || reps < 1 ||
+      !op_list_known(ops, nops, VMEM_OPS, true)) {
     g_err = "vmem walks: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16, reps >= 1 and a list of distinct known ops";
     return -2;
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = grid_of(device, blocks);
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
-  if (!hook_listed || grid > static_cast<unsigned>(MAX_BLOCKS) ||
-      (inject_op >= 0 && (inject_block < 0 || static_cast<unsigned>(inject_block) >= grid || inject_skip_iter >= iters)) ||
+  if (!op_list_has_hook(ops, nops, inject_op) || grid > static_cast<unsigned>(MAX_BLOCKS) ||
+      (inject_op >= 0 && !hook_in_range(inject_block, grid, inject_skip_iter, iters)) ||
       inject_table_word >= static_cast<long long>(VMEM_TABLE_BYTES / 4)) {
     g_err = "vmem walks: inject_op must be in the list, inject_block inside the grid (at most 8192 workgroups), "
             "inject_skip_iter below iters and inject_table_word inside the table";
@@ -611,8 +602,7 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
   }
   for (int k = 0; k < VMEM_OPS; ++k) {
     errors[k] = 0;
-    first[4 * k] = ~0ULL;
-    first[4 * k + 1] = first[4 * k + 2] = first[4 * k + 3] = 0;
+    no_record(first + 4 * k);
     ms[k] = 0.0;
   }
   Run run;
@@ -648,7 +638,7 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
     }
     double total_ms = 0.0;
     for (int r = 0; r <= reps; ++r) {  // r == 0: the warm-up, which carries the hooks
-      const bool hooked = r == 0 && k == inject_op;
+      const HookTrio h = hook_trio(r == 0 && k == inject_op, inject_block, inject_skip_iter);
       const bool table_hook = r == 0 && !store && inject_table_word >= 0;
       if (table_hook)
         if (const int rc = flip_word_bit(static_cast<uint32_t*>(dtable.ptr) + inject_table_word)) return rc;
@@ -659,9 +649,7 @@ int vmem_walks(int device, int blocks, int iters, int reps, const int* ops, int 
         HIP_CHECK(hipGetLastError());
       }
       const WalkLaunch l = {static_cast<uint8_t*>(store ? dregions.ptr : dtable.ptr), store ? region_words * 4u : VMEM_TABLE_BYTES,
-                            static_cast<const uint32_t*>(dexp.ptr), op_seed, iters,
-                            hooked && inject_skip_iter < 0 ? inject_block : -1,
-                            hooked && inject_skip_iter >= 0 ? inject_block : -1, hooked ? inject_skip_iter : -1,
+                            static_cast<const uint32_t*>(dexp.ptr), op_seed, iters, h.flip_block, h.skip_block, h.skip_at,
                             run.rep(), run.map(), static_cast<uint32_t*>(drow.ptr), grid};
       float t = 0.f;
       if (const int rc = run.launch([&] { AllOps::launch[k](l); }, &t)) return rc;
@@ -704,7 +692,7 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = grid_of(device, blocks);
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
   if (grid > static_cast<unsigned>(MAX_BLOCKS)) {
     g_err = "vmem bounds: at most 8192 workgroups";
@@ -712,8 +700,7 @@ int vmem_bounds(int device, int blocks, unsigned int n, uint64_t seed, int leak,
   }
   for (int k = 0; k < 2 * BOUNDS_ROWS; ++k) {
     errors[k] = 0;
-    first[4 * k] = ~0ULL;
-    first[4 * k + 1] = first[4 * k + 2] = first[4 * k + 3] = 0;
+    no_record(first + 4 * k);
     ms[k] = 0.0;
   }
   Run run;
@@ -793,7 +780,7 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = grid_of(device, blocks);
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
   const uint32_t slice_words = slice_bytes / 4;
   if (grid > static_cast<unsigned>(MAX_BLOCKS) ||
@@ -802,7 +789,7 @@ int vmem_l1(int device, int blocks, int reps, unsigned int slice_bytes, int pass
     return -2;
   }
   *errors = 0;
-  first[0] = ~0ULL, first[1] = first[2] = first[3] = 0;
+  no_record(first);
   *ms_plain = *ms_sc1 = 0.0;
   hipFuncAttributes attr;
   HIP_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(l1_kernel<false>)));
@@ -859,12 +846,11 @@ int vmem_ldsdma(int device, int blocks, int iters, int reps, uint64_t seed, unsi
   }
   DeviceScope scope;
   if (const int rc = scope.enter(device)) return rc;
-  const unsigned grid = grid_of(device, blocks);
+  const unsigned grid = default_grid(device, blocks, BLOCKS_PER_CU);
   *blocks_run = static_cast<int>(grid);
   for (int f = 0; f < DMA_FORMS; ++f) {
     errors[f] = 0;
-    first[4 * f] = ~0ULL;
-    first[4 * f + 1] = first[4 * f + 2] = first[4 * f + 3] = 0;
+    no_record(first + 4 * f);
     ms[f] = 0.0;
   }
   Run run;
@@ -879,17 +865,11 @@ int vmem_ldsdma(int device, int blocks, int iters, int reps, uint64_t seed, unsi
     hipFuncAttributes attr;
     HIP_CHECK(DMA_ATTRIBUTES[f](&attr));
     if (const int rc = refuse(attr, DMA_NAMES[f], (THREADS / 64) * 1024)) return rc;
-    double total_ms = 0.0;
-    for (int r = 0; r <= reps; ++r) {
-      float t = 0.f;
-      const auto enqueue = [&] {
-        DMA_LAUNCH[f](grid, static_cast<const uint8_t*>(dtable.ptr), table_seed, vmem_op_seed(seed, 1000 + f + 16 * r), iters,
-                      run.rep(), run.map());
-      };
-      if (const int rc = run.checked(enqueue, &t, errors + f, first + 4 * f)) return rc;
-      if (r > 0) total_ms += t;
-    }
-    ms[f] = total_ms / reps;
+    const auto enqueue = [&](int r) {
+      DMA_LAUNCH[f](grid, static_cast<const uint8_t*>(dtable.ptr), table_seed, vmem_op_seed(seed, 1000 + f + 16 * r), iters,
+                    run.rep(), run.map());
+    };
+    if (const int rc = run.series(reps, enqueue, errors + f, first + 4 * f, ms + f)) return rc;
   }
   if (const int rc = run.read_map(simd_map)) return rc;
   return 0;

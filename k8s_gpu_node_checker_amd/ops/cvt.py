@@ -26,7 +26,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .diag import simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
+from .diag import finish_simd_result, simd_map_summary, simd_name  # noqa: F401  (simd_name: part of this module's interface)
 from .native import bind_cdll
 
 # the native op index (CvtOp of cvt_ref.h): index into OPS
@@ -158,13 +158,8 @@ def cvt_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_ITE
                            "mode": {"round": rnd, "denorm": den, "nearest_even": rnd == MODE_ROUND_NEAREST_EVEN,
                                     "denormals_kept": den == MODE_DENORM_KEPT},
                            "ms": round(sum(r["ms"] for r in rows.values()), 4),
-                           "wall_s": round(time.perf_counter() - t0, 3),
-                           "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_simds:
-        res["bad_simds"] = bad_simds
-    if slots:
-        res["slots"] = seen
-    return res
+                           "wall_s": round(time.perf_counter() - t0, 3)}
+    return finish_simd_result(res, problems, seen, bad_simds, slots)
 
 
 def summary(r: Dict[str, Any]) -> str:

@@ -857,6 +857,19 @@ def simd_map_summary(m: Sequence[int], nrows: int) -> Tuple[List[int], int, List
     return seen, len({r >> 9 for r in seen}), [f"{simd_name(r)} ({m[3 * r + 1]})" for r in seen if m[3 * r + 1]]
 
 
+def finish_simd_result(res: Dict[str, Any], problems: Sequence[str], seen: List[int], bad_simds: List[str],
+                       slots: bool, with_bad: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    """The end of an opt-in diagnostic's result, after its own keys: ``detail`` (the first four ``problems``),
+    ``bad_simds`` where there are any (and with them the keys of ``with_bad``), and on request ``slots``, the rows of
+    :func:`simd_map_summary` that ran a wave."""
+    res["detail"] = "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")
+    if bad_simds:
+        res.update({"bad_simds": bad_simds, **(with_bad or {})})
+    if slots:
+        res["slots"] = seen
+    return res
+
+
 def regfile_test(device: int = 0, rounds: int = 2, seed: int = 0x51D, hold: int = 32, inject_block: int = -1,
                  inject_reg: str = "vgpr_lo") -> Dict[str, Any]:
     """Both vector register files of every SIMD (256 VGPRs + 256 AGPRs x 64 lanes = 128 KiB) under four patterns,

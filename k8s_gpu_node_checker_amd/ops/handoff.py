@@ -36,7 +36,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .diag import simd_map_summary, simd_name, slot_name
+from .diag import finish_simd_result, simd_map_summary, simd_name, slot_name
 from .native import bind_cdll
 
 # the native row index is FORMS.index(form) * 2 + PLACEMENTS.index(placement) (handoff_ref.h)
@@ -190,13 +190,8 @@ def handoff_test(device: int = 0, rows: Sequence[str] = ROWS, rounds: int = DEFA
     total = sum(r["errors"] for r in out.values())
     res: Dict[str, Any] = {"pass": total == 0, "errors": total, "complete": all(r["complete"] for r in out.values()),
                            "simds": len(seen), "xcds": xcds, "blocks": ran.value, "rounds": int(rounds), "rows": out,
-                           "ms": round(sum(r["ms"] for r in out.values()), 4), "wall_s": round(wall, 3),
-                           "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_simds:
-        res["bad_simds"] = bad_simds
-    if slots:
-        res["slots"] = seen
-    return res
+                           "ms": round(sum(r["ms"] for r in out.values()), 4), "wall_s": round(wall, 3)}
+    return finish_simd_result(res, problems, seen, bad_simds, slots)
 
 
 def summary(r: Dict[str, Any]) -> str:

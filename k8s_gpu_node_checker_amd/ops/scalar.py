@@ -26,7 +26,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .diag import simd_map_summary, simd_name
+from .diag import finish_simd_result, simd_map_summary, simd_name
 from .native import bind_cdll
 
 # the native op index (ScalarOp of scalar_ref.h): index into this
@@ -271,13 +271,8 @@ def scalar_test(device: int = 0, parts: Sequence[str] = PARTS, ops: Sequence[str
     total = sum(p["errors"] for p in out_parts.values())
     res: Dict[str, Any] = {"pass": total == 0, "errors": total, "simds": len(seen), "xcds": xcds,
                            "blocks": grids, "parts": out_parts, "ms": round(sum(p["ms"] for p in out_parts.values()), 4),
-                           "wall_s": round(time.perf_counter() - t0, 3),
-                           "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_simds:
-        res["bad_simds"] = bad_simds
-    if slots:
-        res["slots"] = seen
-    return res
+                           "wall_s": round(time.perf_counter() - t0, 3)}
+    return finish_simd_result(res, problems, seen, bad_simds, slots)
 
 
 def summary(r: Dict[str, Any]) -> str:

@@ -29,7 +29,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .diag import simd_map_summary, simd_name
+from .diag import finish_simd_result, simd_map_summary, simd_name
 from .native import bind_cdll
 
 ISOLATE_ROW = "isolate/1k"
@@ -165,13 +165,8 @@ def scratch_test(device: int = 0, rows: Sequence[str] = ROWS, blocks: Optional[i
                            "rows": out, "frame_bytes": part,
                            "co_resident_waves": int(info[0]), "backing_bytes": int(info[1]),
                            "backing_peak_bytes": int(info[2]), "ms": round(sum(r["ms"] for r in out.values()), 4),
-                           "wall_s": round(wall, 3),
-                           "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_simds:
-        res["bad_simds"] = bad_simds
-    if slots:
-        res["slots"] = seen
-    return res
+                           "wall_s": round(wall, 3)}
+    return finish_simd_result(res, problems, seen, bad_simds, slots)
 
 
 def summary(r: Dict[str, Any]) -> str:

@@ -33,7 +33,7 @@ import ctypes
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .diag import simd_map_summary
+from .diag import finish_simd_result, simd_map_summary
 from .lanes import simd_name
 from .native import bind_cdll
 
@@ -270,14 +270,9 @@ def vmem_test(device: int = 0, ops: Sequence[str] = OPS, iters: int = DEFAULT_IT
                            "blocks": grid, "iters": int(iters), "ops": rows, "bounds": bounds, "l1": l1, "ldsdma": ldsdma,
                            "ms": round(sum(r["ms"] for r in rows.values()) + bounds["ms"] + l1["ms"] + l1["ms_sc1"]
                                        + ldsdma["ms"], 4),
-                           "wall_s": round(time.perf_counter() - t0, 3),
-                           "detail": "; ".join(problems[:4]) + (" ..." if len(problems) > 4 else "")}
-    if bad_simds:
-        res["bad_simds"] = bad_simds
-        res["bad_cus"] = sorted({cu_name(r) for r in seen if total_map[3 * r + 1]})
-    if slots:
-        res["slots"] = seen
-    return res
+                           "wall_s": round(time.perf_counter() - t0, 3)}
+    return finish_simd_result(res, problems, seen, bad_simds, slots,
+                              {"bad_cus": sorted({cu_name(r) for r in seen if total_map[3 * r + 1]})})
 
 
 def summary(r: Dict[str, Any]) -> str:

@@ -655,7 +655,51 @@ class FakeHbmscanLib:
         return 0
 
 
-class FakeLanesLib:
+class _SimdFake:
+    """What the stand-ins of the SIMD-located libraries share: the node (``n`` GPUs of ``xcds`` x 32 CUs, a launch
+    ``ms`` long), the wrong results asked for (``bad``, all on SIMD map row ``bad_row``), the one GPU a narrowed process
+    sees (``physical``), the ``calls`` log and the last error."""
+
+    SLOTS = 4096
+    BAD_ROW = (((5 << 7) | (1 << 5) | 7) << 2) | 2  # xcd5/se1/cu7/simd2
+
+    def __init__(self, n, bad, bad_row, xcds, ms, physical):
+        self.n, self.bad, self.bad_row, self.xcds, self.ms, self.physical = n, dict(bad or {}), bad_row, xcds, ms, physical
+        self.calls: List[str] = []
+        self.err = b"boom"
+
+    def _count(self) -> int:
+        return self.n if self.physical is None else 1
+
+    def _device(self, device: int, log: Optional[str] = None) -> Optional[int]:
+        """The node's ordinal of ``device`` (logged as ``{log}{ordinal}``), None with the error set when a narrowed
+        process asks for another than its own."""
+        if self.physical is not None:
+            if device != 0:
+                self.err = b"hipSetDevice(device): invalid device ordinal"
+                return None
+            device = self.physical
+        if log is not None:
+            self.calls.append(f"{log}{device}")
+        return device
+
+    def _fill_map(self, simd_map, grid: int, launches: int, ticks: int) -> None:
+        """``launches`` launches of ``grid`` workgroups, ``ticks`` long each, and nothing wrong."""
+        for r in range(3 * self.SLOTS):
+            simd_map[r] = 0
+        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
+                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
+        for r in rows:
+            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
+            simd_map[3 * r + 2] = ticks * launches
+
+    def _blame(self, simd_map, wrong: int) -> None:
+        """``wrong`` (> 0) wrong words on ``bad_row``."""
+        simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
+        simd_map[3 * self.bad_row + 1] += wrong
+
+
+class FakeLanesLib(_SimdFake):
     """``libmi355x_lanes.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD.
 
     bad:      ``{(device, op index): wrong lanes}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the
@@ -664,34 +708,27 @@ class FakeLanesLib:
     Calls are logged as ``lanes{device}`` in ``calls``: empty = never called."""
 
     OPS = 39
-    SLOTS = 4096
     WANT = 0x5EED1A9E
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.2,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.2,
                  physical: Optional[int] = None):
-        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
-        self.physical = physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
 
     def lanes_last_error(self) -> bytes:
         return self.err
 
     def lanes_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def lanes_slots(self) -> int:
         return self.SLOTS
 
     def lanes_test(self, device, blocks, iters, reps, op_mask, seed, inject_op, inject_block, inject_skip_iter,
                    errors, first_where, got, want, ms, simd_map, blocks_run):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"lanes{device}")
+        device = self._device(device, "lanes")
+        if device is None:
+            return -1
         if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not op_mask \
                 or op_mask >> self.OPS:
             self.err = (b"lanes test: need a valid device, blocks >= 0 (0: 4 per CU), iters 1..2^20, reps >= 1 and a "
@@ -699,14 +736,7 @@ class FakeLanesLib:
             return -2
         grid = blocks or self.xcds * 32 * 4
         _put(blocks_run, ctypes.c_int, grid)
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        launches = (reps + 1) * bin(op_mask).count("1")
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = 1000 * iters * launches
+        self._fill_map(simd_map, grid, (reps + 1) * bin(op_mask).count("1"), 1000 * iters)
         for k in range(self.OPS):
             on = bool((op_mask >> k) & 1)
             wrong = self.bad.get((device, k), 0) if on else 0
@@ -718,8 +748,7 @@ class FakeLanesLib:
             got[k] = self.WANT ^ 0x100 if wrong else 0
             ms[k] = self.ms if on else 0.0
             if wrong:
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
         return 0
 
     def lanes_apply(self, device, op, iter, x_in, y_in, x_out, y_out):
@@ -735,7 +764,7 @@ def cvt_c_ops() -> List[str]:
         return re.findall(r'^\s*X\((\w+), "v_cvt_\w+", CG_', f.read(), re.M)
 
 
-class FakeCvtLib:
+class FakeCvtLib(_SimdFake):
     """``libmi355x_cvt.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD, the waves in
     float mode ``mode`` (MODE bits 7:0; 0xf0: round-to-nearest-even, denormals kept).
 
@@ -745,22 +774,19 @@ class FakeCvtLib:
     Calls are logged as ``cvt{device}`` in ``calls``: empty = never called."""
 
     OPS = len(cvt_c_ops())  # the op table's length, read from cvt_ref.h: nothing repeats the count
-    SLOTS = 4096
     WANT = 0x5EEDC0A7
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.05,
                  mode: int = 0xf0, physical: Optional[int] = None):
-        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
-        self.float_mode, self.physical = mode, physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
+        self.float_mode = mode
 
     def cvt_last_error(self) -> bytes:
         return self.err
 
     def cvt_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def cvt_slots(self) -> int:
         return self.SLOTS
@@ -782,12 +808,9 @@ class FakeCvtLib:
 
     def cvt_test(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
                  errors, first, ms, mode, simd_map, blocks_run):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"cvt{device}")
+        device = self._device(device, "cvt")
+        if device is None:
+            return -1
         chosen = [ops[i] for i in range(nops)] if 1 <= nops <= self.OPS else []
         if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 16 or reps < 1 or not chosen \
                 or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
@@ -804,14 +827,7 @@ class FakeCvtLib:
             field = b"FP_ROUND" if self.float_mode & 0xf else b"FP_DENORM"
             self.err = b"cvt test: the waves run with MODE." + field + b": the model holds for another"
             return -3
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        launches = (reps + 1) * len(chosen)
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = 1000 * iters * launches
+        self._fill_map(simd_map, grid, (reps + 1) * len(chosen), 1000 * iters)
         for k in range(self.OPS):
             on = k in chosen
             wrong = self.bad.get((device, k), 0) if on else 0
@@ -824,8 +840,7 @@ class FakeCvtLib:
             first[4 * k + 3] = self.WANT if wrong else 0
             ms[k] = self.ms if on else 0.0
             if wrong:
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
         return 0
 
     def cvt_apply_many(self, device, op, rows, nrows, out):
@@ -833,7 +848,7 @@ class FakeCvtLib:
         return -1
 
 
-class FakeIfetchLib:
+class FakeIfetchLib(_SimdFake):
     """``libmi355x_ifetch.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row of both parts clean on every
     SIMD, the walk kernel's blocks ``BLOCK_BYTES`` apart.
 
@@ -845,23 +860,19 @@ class FakeIfetchLib:
 
     OPS = 10
     NB = 1024
-    SLOTS = 4096
     BLOCK_BYTES = 456
     WANT = 0x1FE7C4ED
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, str, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.05,
                  physical: Optional[int] = None):
-        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
-        self.physical = physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
 
     def ifetch_last_error(self) -> bytes:
         return self.err
 
     def ifetch_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def ifetch_slots(self) -> int:
         return self.SLOTS
@@ -874,23 +885,6 @@ class FakeIfetchLib:
             addrs[b] = 0x7f0000100000 + self.BLOCK_BYTES * (self.NB - 1 - b)
         return 0
 
-    def _device(self, device):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return None
-            return self.physical
-        return device
-
-    def _fill_map(self, simd_map, grid, launches, ticks):
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = ticks * launches
-
     def _record(self, first, k, wrong, where):
         first[4 * k] = where if wrong else (1 << 64) - 1
         first[4 * k + 1] = 0
@@ -899,10 +893,9 @@ class FakeIfetchLib:
 
     def ifetch_walk_test(self, device, blocks, steps, reps, nbs, nrows, seed, inject_row, inject_block, inject_skip_step,
                          errors, first, ms, footprint, visited, simd_map, blocks_run):
-        device = self._device(device)
+        device = self._device(device, "ifetch_walk")
         if device is None:
             return -1
-        self.calls.append(f"ifetch_walk{device}")
         rows = [nbs[i] for i in range(nrows)] if 1 <= nrows <= 64 else []
         if not 0 <= device < self.n or blocks < 0 or not 1 <= steps <= 1 << 16 or reps < 1 or not rows \
                 or not all(1 <= v <= self.NB for v in rows):
@@ -928,16 +921,14 @@ class FakeIfetchLib:
             footprint[k] = self.BLOCK_BYTES * nb
             visited[k] = nb
             if wrong:
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
         return 0
 
     def ifetch_branch_test(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
                            errors, first, ms, simd_map, blocks_run):
-        device = self._device(device)
+        device = self._device(device, "ifetch_branch")
         if device is None:
             return -1
-        self.calls.append(f"ifetch_branch{device}")
         chosen = [ops[i] for i in range(nops)] if 1 <= nops <= self.OPS else []
         if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not chosen \
                 or not all(0 <= k < self.OPS for k in chosen):
@@ -958,8 +949,7 @@ class FakeIfetchLib:
             self._record(first, k, wrong, (self.bad_row << 16) | 1)
             ms[k] = self.ms if on else 0.0
             if wrong:
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
         return 0
 
     def ifetch_apply_blocks(self, device, blocks, n, x, p, x_out, p_out):
@@ -971,7 +961,7 @@ class FakeIfetchLib:
         return -1
 
 
-class FakeHandoffLib:
+class FakeHandoffLib(_SimdFake):
     """``libmi355x_handoff.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row clean and complete, block b on
     CU ``b // xcds`` of XCD ``b % xcds`` (so ``cross`` pairs lie on different XCDs and ``same`` pairs on one).
 
@@ -986,25 +976,22 @@ class FakeHandoffLib:
     Calls are logged as ``handoff{device}`` in ``calls``: empty = never called."""
 
     ROWS = 8
-    SLOTS = 4096
     LDS = 81 * 1024
     WANT = 0x4A2D0FF1
     STALE = 0x0DD0FF1C
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None, corrupt: Tuple[int, ...] = (),
                  timeout: Optional[Dict[Tuple[int, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.4,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.4,
                  physical: Optional[int] = None):
-        self.n, self.bad, self.corrupt, self.timeout = n, dict(bad or {}), set(corrupt), dict(timeout or {})
-        self.bad_row, self.xcds, self.ms, self.physical = bad_row, xcds, ms, physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
+        self.corrupt, self.timeout = set(corrupt), dict(timeout or {})
 
     def handoff_last_error(self) -> bytes:
         return self.err
 
     def handoff_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def handoff_slots(self) -> int:
         return self.SLOTS
@@ -1019,12 +1006,9 @@ class FakeHandoffLib:
     def handoff_test(self, device, blocks, rounds, reps, rows, nrows, seed, spin_ms, jitter, inject_row, inject_block,
                      inject_round, inject_stale_word, inject_mute, errors, words, timeouts, first, tmo, pairs, ms,
                      simd_map, blocks_run):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"handoff{device}")
+        device = self._device(device, "handoff")
+        if device is None:
+            return -1
         chosen = [rows[i] for i in range(nrows)] if 1 <= nrows <= self.ROWS else []
         if not 0 <= device < self.n or not 1 <= rounds <= 1 << 15 or reps < 1 or not 1 <= spin_ms <= 1000 or not chosen \
                 or not all(0 <= k < self.ROWS for k in chosen):
@@ -1076,8 +1060,7 @@ class FakeHandoffLib:
                 cls = 2 if k in self.corrupt else 1
                 record = ((self.bad_row << 16) | 9, 3, 5, 37, self.WANT ^ 0x100 if cls == 2 else self.STALE, self.WANT,
                           cls, 0 if cls == 2 else 1, 1)
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
             waits = self.timeout.get((device, k), 0)
             gave_up = (2, 1, 3, 5) if waits else None
             if k == inject_row:
@@ -1109,7 +1092,7 @@ class FakeHandoffLib:
         return 0
 
 
-class FakeScratchLib:
+class FakeScratchLib(_SimdFake):
     """``libmi355x_scratch.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every row clean, wave w on SIMD ``w % 4``
     of CU ``(w // 4) // xcds % 32`` of XCD ``(w // 4) % xcds``.
 
@@ -1121,26 +1104,23 @@ class FakeScratchLib:
     The hooks act as the library's do: exactly one wrong word of the hook's class in the warm-up launch.
     Calls are logged as ``scratch{device}`` in ``calls``: empty = never called."""
 
-    SLOTS = 4096
     WANT = 0x5C7A7C11
     FRAME = {"isolate": 1040, "index": 272, "calls": 400}
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
-                 classes: Optional[Dict[int, str]] = None, bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2,
+                 classes: Optional[Dict[int, str]] = None, bad_row: int = _SimdFake.BAD_ROW,
                  xcds: int = 8, ms: float = 0.05, physical: Optional[int] = None):
         from ..ops import scratch as ops_scratch
         self.rows = len(ops_scratch.ROWS)
         self.iso, self.index, self.calls_row = self.rows - 3, self.rows - 2, self.rows - 1
-        self.n, self.bad, self.classes = n, dict(bad or {}), dict(classes or {})
-        self.bad_row, self.xcds, self.ms, self.physical = bad_row, xcds, ms, physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
+        self.classes = dict(classes or {})
 
     def scratch_last_error(self) -> bytes:
         return self.err
 
     def scratch_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def scratch_slots(self) -> int:
         return self.SLOTS
@@ -1156,12 +1136,9 @@ class FakeScratchLib:
     def scratch_test(self, device, rows, nrows, blocks, iso_blocks, rounds, reps, seed, inject_row,
                      inject_wave, inject_round, inject_alias, inject_stale_word, errors, words, ms, first, frame_bytes,
                      info, simd_map):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"scratch{device}")
+        device = self._device(device, "scratch")
+        if device is None:
+            return -1
         chosen = [rows[i] for i in range(nrows)] if 1 <= nrows <= self.rows else []
         if not 0 <= device < self.n or not 1 <= rounds <= 16 or reps < 1 \
                 or blocks < 0 or iso_blocks < 0 or not chosen or not all(0 <= k < self.rows for k in chosen):
@@ -1224,8 +1201,7 @@ class FakeScratchLib:
                 cell = (1 << 28) | (3 << 14) | (9 << 8) | 37 if k == self.iso else 37
                 record = ((self.bad_row << 16) | 9, 3, cell, self.WANT ^ 0x100, self.WANT, cls, 1 if cls == 2 else 0,
                           4 if cls == 1 else (1 << 64) - 1, self._simd(4) if cls == 1 else 0, 1)
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
             if k == inject_row:
                 row = self._simd(inject_wave)
                 if inject_alias:
@@ -1247,7 +1223,7 @@ class FakeScratchLib:
         return 0
 
 
-class FakeMatrixLib:
+class FakeMatrixLib(_SimdFake):
     """``libmi355x_matrix.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every op clean on every SIMD.
 
     bad:      ``{(device, op index): wrong elements}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the
@@ -1256,34 +1232,27 @@ class FakeMatrixLib:
     Calls are logged as ``matrix{device}`` in ``calls``: empty = never called."""
 
     OPS = 34
-    SLOTS = 4096
     WANT = 0x4A82C64E
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.2,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.2,
                  physical: Optional[int] = None):
-        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
-        self.physical = physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
 
     def matrix_last_error(self) -> bytes:
         return self.err
 
     def matrix_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def matrix_slots(self) -> int:
         return self.SLOTS
 
     def matrix_test(self, device, blocks, iters, reps, ops, n_ops, seed, inject_op, inject_block, inject_skip_step,
                     errors, first_where, got, want, ms, simd_map, blocks_run):
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"matrix{device}")
+        device = self._device(device, "matrix")
+        if device is None:
+            return -1
         chosen = [int(ops[i]) for i in range(n_ops)]
         if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not chosen \
                 or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
@@ -1292,14 +1261,7 @@ class FakeMatrixLib:
             return -2
         grid = blocks or self.xcds * 32 * 2
         _put(blocks_run, ctypes.c_int, grid)
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        launches = (reps + 1) * len(chosen)
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = 1000 * iters * launches
+        self._fill_map(simd_map, grid, (reps + 1) * len(chosen), 1000 * iters)
         for k in range(self.OPS):
             on = k in chosen
             wrong = self.bad.get((device, k), 0) if on else 0
@@ -1311,8 +1273,7 @@ class FakeMatrixLib:
             got[k] = self.WANT ^ 0x100 if wrong else 0
             ms[k] = self.ms if on else 0.0
             if wrong:
-                simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-                simd_map[3 * self.bad_row + 1] += wrong
+                self._blame(simd_map, wrong)
         return 0
 
     def matrix_apply(self, device, op, a, b, c, idx, scale_a, scale_b, d):
@@ -1320,7 +1281,7 @@ class FakeMatrixLib:
         return -1
 
 
-class FakeVmemLib:
+class FakeVmemLib(_SimdFake):
     """``libmi355x_vmem.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every part clean on every SIMD.
 
     bad:      ``{(device, op index): wrong words}``, all on SIMD map row ``bad_row`` (xcd5/se1/cu7/simd2), the first
@@ -1331,23 +1292,20 @@ class FakeVmemLib:
 
     OPS = 59
     LOADS = 36
-    SLOTS = 4096
     WANT = 0x4A82C64E
     FORMS = (b"global_load_lds_dword", b"global_load_lds_dwordx4", b"buffer_load_dword_lds", b"buffer_load_dwordx4_lds")
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, int], int]] = None,
-                 bad_l1: Optional[Dict[int, int]] = None, bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2,
+                 bad_l1: Optional[Dict[int, int]] = None, bad_row: int = _SimdFake.BAD_ROW,
                  xcds: int = 8, ms: float = 0.2, physical: Optional[int] = None):
-        self.n, self.bad, self.bad_l1, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), dict(bad_l1 or {}), bad_row, xcds, ms
-        self.physical = physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
+        self.bad_l1 = dict(bad_l1 or {})
 
     def vmem_last_error(self) -> bytes:
         return self.err
 
     def vmem_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def vmem_slots(self) -> int:
         return self.SLOTS
@@ -1364,37 +1322,17 @@ class FakeVmemLib:
             return -2
         return (op + word) & 1
 
-    def _device(self, device: int) -> int:
-        """The node's ordinal of ``device``, -1 (with the error set) when a narrowed process asks for another."""
-        if self.physical is None:
-            return device
-        if device != 0:
-            self.err = b"hipSetDevice(device): invalid device ordinal"
-            return -1
-        return self.physical
-
     def _grid(self, blocks, blocks_run, simd_map, launches, ticks) -> int:
         grid = blocks or self.xcds * 32 * 2
         _put(blocks_run, ctypes.c_int, grid)
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = ticks * launches
+        self._fill_map(simd_map, grid, launches, ticks)
         return grid
-
-    def _blame(self, simd_map, wrong: int) -> None:
-        simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-        simd_map[3 * self.bad_row + 1] += wrong
 
     def vmem_walks(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
                    inject_table_word, errors, first, ms, simd_map, blocks_run):
-        device = self._device(device)
-        if device < 0:
+        device = self._device(device, "vmem")
+        if device is None:
             return -1
-        self.calls.append(f"vmem{device}")
         chosen = [int(ops[i]) for i in range(nops)]
         if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1 <= iters <= 1 << 16 or reps < 1 or not chosen \
                 or len(set(chosen)) != len(chosen) or not all(0 <= k < self.OPS for k in chosen):
@@ -1421,7 +1359,7 @@ class FakeVmemLib:
 
     def vmem_bounds(self, device, blocks, n, seed, leak, errors, first, ms, simd_map, blocks_run):
         device = self._device(device)
-        if device < 0:
+        if device is None:
             return -1
         if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1024 <= n <= 65536 or n & (n - 1):
             self.err = (b"vmem bounds: need a valid device, blocks 0..8192 (0: 2 per CU) and n a power of two from 1 KiB "
@@ -1443,7 +1381,7 @@ class FakeVmemLib:
     def vmem_l1(self, device, blocks, reps, slice_bytes, passes, seed, inject_block, inject_word, errors, first, ms_plain,
                 ms_sc1, simd_map, blocks_run):
         device = self._device(device)
-        if device < 0:
+        if device is None:
             return -1
         if not 0 <= device < self.n or not 0 <= blocks <= 8192 or reps < 1 or not 1024 <= slice_bytes <= 1 << 20 \
                 or slice_bytes & (slice_bytes - 1) or not 1 <= passes <= 65536:
@@ -1475,7 +1413,7 @@ class FakeVmemLib:
 
     def vmem_ldsdma(self, device, blocks, iters, reps, seed, errors, first, ms, simd_map, blocks_run):
         device = self._device(device)
-        if device < 0:
+        if device is None:
             return -1
         if not 0 <= device < self.n or not 0 <= blocks <= 8192 or not 1 <= iters <= 1 << 16 or reps < 1:
             self.err = b"vmem ldsdma: need a valid device, blocks 0..8192 (0: 2 per CU), iters 1..2^16 and reps >= 1"
@@ -1598,7 +1536,7 @@ def scalar_model(op: str, a: int, b: int, scc: int) -> Tuple[int, int]:
     return r, (scc & 1 if rule == keep else int(r != 0) if rule == nz else int(bool(rule)))
 
 
-class FakeScalarLib:
+class FakeScalarLib(_SimdFake):
     """``libmi355x_scalar.so`` for a node of ``n`` GPUs of ``xcds`` x 32 CUs: every part clean on every SIMD, and
     ``scalar_apply`` answered by :func:`scalar_model`.
 
@@ -1610,23 +1548,19 @@ class FakeScalarLib:
 
     OPS = 83
     KINDS = 7
-    SLOTS = 4096
     SGPR_LO, SGPR_HI, SGPR_REGS = 20, 95, 75
     WANT = 0x5CA1A29E
 
     def __init__(self, n: int = 8, bad: Optional[Dict[Tuple[int, str, int], int]] = None,
-                 bad_row: int = (((5 << 7) | (1 << 5) | 7) << 2) | 2, xcds: int = 8, ms: float = 0.05,
+                 bad_row: int = _SimdFake.BAD_ROW, xcds: int = 8, ms: float = 0.05,
                  physical: Optional[int] = None):
-        self.n, self.bad, self.bad_row, self.xcds, self.ms = n, dict(bad or {}), bad_row, xcds, ms
-        self.physical = physical
-        self.calls: List[str] = []
-        self.err = b"boom"
+        super().__init__(n, bad, bad_row, xcds, ms, physical)
 
     def scalar_last_error(self) -> bytes:
         return self.err
 
     def scalar_device_count(self) -> int:
-        return self.n if self.physical is None else 1
+        return self._count()
 
     def scalar_slots(self) -> int:
         return self.SLOTS
@@ -1640,34 +1574,10 @@ class FakeScalarLib:
     def scalar_sgpr_regs(self) -> int:
         return self.SGPR_REGS
 
-    def _device(self, device: int, part: str) -> int:
-        """The node's ordinal of ``device`` (logged), or -1 with the error set."""
-        if self.physical is not None:
-            if device != 0:
-                self.err = b"hipSetDevice(device): invalid device ordinal"
-                return -1
-            device = self.physical
-        self.calls.append(f"{part}{device}")
-        return device
-
-    def _map(self, simd_map, grid: int, per_cu: int, launches: int, ticks: int) -> None:
-        for r in range(3 * self.SLOTS):
-            simd_map[r] = 0
-        rows = [(((x << 7) | (se << 5) | cu) << 2) | simd for x in range(self.xcds) for se in range(4)
-                for cu in range(8) for simd in range(4)][:4 * grid]  # a workgroup's 4 waves: one per SIMD of a CU
-        for r in rows:
-            simd_map[3 * r] = max(1, 4 * grid // len(rows)) * launches
-            simd_map[3 * r + 2] = ticks * launches
-
-    def _wrong(self, simd_map, wrong: int) -> None:
-        if wrong:
-            simd_map[3 * self.bad_row] = max(1, simd_map[3 * self.bad_row])
-            simd_map[3 * self.bad_row + 1] += wrong
-
     def scalar_salu(self, device, blocks, iters, reps, ops, nops, seed, inject_op, inject_block, inject_skip_iter,
                     errors, first_where, got, want, ms, simd_map, blocks_run):
         device = self._device(device, "salu")
-        if device < 0:
+        if device is None:
             return -1
         listed = [ops[i] for i in range(max(0, nops))]
         if not 0 <= device < self.n or blocks < 0 or not 1 <= iters <= 1 << 20 or reps < 1 or not listed \
@@ -1677,7 +1587,7 @@ class FakeScalarLib:
             return -2
         grid = blocks or self.xcds * 32 * 4
         _put(blocks_run, ctypes.c_int, grid)
-        self._map(simd_map, grid, 4, (reps + 1) * len(listed), 1000 * iters)
+        self._fill_map(simd_map, grid, (reps + 1) * len(listed), 1000 * iters)
         for k in range(self.OPS):
             on = k in listed
             wrong = self.bad.get((device, "salu", k), 0) if on else 0
@@ -1688,13 +1598,14 @@ class FakeScalarLib:
             want[k] = self.WANT if wrong else 0
             got[k] = self.WANT ^ 0x100 if wrong else 0
             ms[k] = self.ms if on else 0.0
-            self._wrong(simd_map, wrong)
+            if wrong:
+                self._blame(simd_map, wrong)
         return 0
 
     def scalar_sgpr(self, device, blocks, reps, hold, seed, inject_block, inject_reg, errors, first_where, got, want,
                     ms, simd_map, blocks_run):
         device = self._device(device, "sgpr")
-        if device < 0:
+        if device is None:
             return -1
         if not 0 <= device < self.n or blocks < 0 or reps < 1 or not 0 <= hold <= 65536 or not -1 <= inject_reg <= 1:
             self.err = (b"scalar sgpr: need a valid device, blocks >= 0 (0: 7 per CU), reps >= 1, hold 0..65536 and "
@@ -1702,7 +1613,7 @@ class FakeScalarLib:
             return -2
         grid = blocks or self.xcds * 32 * 7
         _put(blocks_run, ctypes.c_int, grid)
-        self._map(simd_map, grid, 7, reps + 1, 4000 * (hold + 1))
+        self._fill_map(simd_map, grid, reps + 1, 4000 * (hold + 1))
         wrong = self.bad.get((device, "sgpr", 0), 0) + (inject_reg >= 0)
         reg = (self.SGPR_LO, self.SGPR_HI)[inject_reg] if inject_reg >= 0 else 41
         _put(errors, ctypes.c_ulonglong, wrong)
@@ -1711,13 +1622,14 @@ class FakeScalarLib:
         _put(want, ctypes.c_ulonglong, self.WANT if wrong else 0)
         _put(got, ctypes.c_ulonglong, self.WANT ^ (0x10 if inject_reg >= 0 else 0x100) if wrong else 0)
         _put(ms, ctypes.c_double, self.ms)
-        self._wrong(simd_map, wrong)
+        if wrong:
+            self._blame(simd_map, wrong)
         return 0
 
     def scalar_smem(self, device, blocks, reps, small_bytes, large_bytes, passes, loads, kind_mask, seed, inject_word,
                     errors, first_where, got, want, ms_hit, ms_miss, simd_map, blocks_run):
         device = self._device(device, "smem")
-        if device < 0:
+        if device is None:
             return -1
         sized = all(64 <= b <= 1 << 26 and b & (b - 1) == 0 for b in (small_bytes, large_bytes))
         if not 0 <= device < self.n or blocks < 0 or reps < 1 or not sized or not 1 <= passes <= 4096 \
@@ -1728,7 +1640,7 @@ class FakeScalarLib:
             return -2
         grid = blocks or self.xcds * 32 * 4
         _put(blocks_run, ctypes.c_int, grid)
-        self._map(simd_map, grid, 4, 2 * (reps + 1) * bin(kind_mask).count("1"), 200 * (passes + loads))
+        self._fill_map(simd_map, grid, 2 * (reps + 1) * bin(kind_mask).count("1"), 200 * (passes + loads))
         for k in range(self.KINDS):
             on = bool((kind_mask >> k) & 1)
             wrong = self.bad.get((device, "smem", k), 0) if on else 0
@@ -1740,7 +1652,8 @@ class FakeScalarLib:
             got[k] = self.WANT ^ (0x10 if inject_word >= 0 else 0x100) if wrong else 0
             ms_hit[k] = self.ms if on else 0.0
             ms_miss[k] = 2 * self.ms if on else 0.0
-            self._wrong(simd_map, wrong)
+            if wrong:
+                self._blame(simd_map, wrong)
         return 0
 
     def scalar_apply(self, device, op, n, a, b, scc_in, result, scc_out):
@@ -1841,16 +1754,17 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
             lanes: Optional[Dict] = None, scalar: Optional[Dict] = None, matrix: Optional[Dict] = None,
             vmem: Optional[Dict] = None, cvt: Optional[Dict] = None, hbmscan: Optional[Dict] = None, ifetch: Optional[Dict] = None,
             handoff: Optional[Dict] = None, scratch: Optional[Dict] = None, **diag_kw) -> None:
-    """Make this process's ``ops.diag``, ``ops.fabric``, ``ops.xgmi``, ``ops.atomics``, ``ops.lanes``, ``ops.scalar``
-    (and ``ops.matrix``: ``FakeMatrixLib(n, **matrix)``; ``ops.vmem``: ``FakeVmemLib(n, **vmem)``; ``ops.cvt``: ``FakeCvtLib(n, **cvt)``; ``ops.hbmscan``: ``FakeHbmscanLib(n, **hbmscan)``; ``ops.ifetch``: ``FakeIfetchLib(n, **ifetch)``; ``ops.handoff``: ``FakeHandoffLib(n, **handoff)``; ``ops.scratch``: ``FakeScratchLib(n, **scratch)``)
-    use the fakes: ``FakeDiagLib(n, **diag_kw)``, ``FakeFabricLib(**fabric)``, ``FakeXgmiLib(n, **xgmi)``,
-    ``FakeAtomicsLib(n, **atomics)``, ``FakeLanesLib(n, **lanes)`` and ``FakeScalarLib(n, **scalar)``.  The node agent's diagnostic children run it first when the agent is given
-    ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py), so the
-    child code path runs unchanged on CPU with scripted GPUs; a child narrowed to one GPU (``HIP_VISIBLE_DEVICES``)
-    sees only that one, as under HIP."""
+    """Make this process's ``ops.diag``, ``ops.fabric`` and ``ops.xgmi`` use the fakes ``FakeDiagLib(n, **diag_kw)``,
+    ``FakeFabricLib(**fabric)`` and ``FakeXgmiLib(n, **xgmi)``, and the module ``ops.X`` of every opt-in diagnostic X
+    of ``ops/optin.OPT_IN`` its ``FakeXLib(n, **X)``.  The node agent's diagnostic children run it first when the agent
+    is given ``diag_setup=("k8s_gpu_node_checker_amd.testing.fake_native", "install", {...})`` (agent/isolation.py),
+    so the child code path runs unchanged on CPU with scripted GPUs; a child narrowed to one GPU
+    (``HIP_VISIBLE_DEVICES``) sees only that one, as under HIP."""
+    import importlib
     import os
     from ..ops import diag
     from ..ops import fabric as fabric_mod
+    from ..ops.optin import OPT_IN
     lib: object = FakeDiagLib(n=n, **diag_kw)
     vis = os.environ.get("HIP_VISIBLE_DEVICES", "").strip()
     if vis.isdigit() and int(vis) < n:
@@ -1860,33 +1774,9 @@ def install(n: int = 1, fabric: Optional[Dict] = None, xgmi: Optional[Dict] = No
     from ..ops import xgmi as xgmi_mod
     xlib = FakeXgmiLib(n=n, **(xgmi or {}))
     xgmi_mod.lib = lambda: xlib
-    from ..ops import atomics as atomics_mod
-    alib = FakeAtomicsLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(atomics or {}))
-    atomics_mod.lib = lambda: alib
-    from ..ops import lanes as lanes_mod
-    llib = FakeLanesLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(lanes or {}))
-    lanes_mod.lib = lambda: llib
-    from ..ops import scalar as scalar_mod
-    slib = FakeScalarLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(scalar or {}))
-    scalar_mod.lib = lambda: slib
-    from ..ops import matrix as matrix_mod
-    mlib = FakeMatrixLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(matrix or {}))
-    matrix_mod.lib = lambda: mlib
-    from ..ops import vmem as vmem_mod
-    vlib = FakeVmemLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(vmem or {}))
-    vmem_mod.lib = lambda: vlib
-    from ..ops import cvt as cvt_mod
-    clib = FakeCvtLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(cvt or {}))
-    cvt_mod.lib = lambda: clib
-    from ..ops import hbmscan as hbmscan_mod
-    hlib = FakeHbmscanLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(hbmscan or {}))
-    hbmscan_mod.lib = lambda: hlib
-    from ..ops import ifetch as ifetch_mod
-    ilib = FakeIfetchLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(ifetch or {}))
-    ifetch_mod.lib = lambda: ilib
-    from ..ops import handoff as handoff_mod
-    holib = FakeHandoffLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(handoff or {}))
-    handoff_mod.lib = lambda: holib
-    from ..ops import scratch as scratch_mod
-    sclib = FakeScratchLib(n=n, physical=int(vis) if vis.isdigit() and int(vis) < n else None, **(scratch or {}))
-    scratch_mod.lib = lambda: sclib
+    physical = int(vis) if vis.isdigit() and int(vis) < n else None
+    given = {"atomics": atomics, "lanes": lanes, "scalar": scalar, "matrix": matrix, "vmem": vmem, "cvt": cvt,
+             "hbmscan": hbmscan, "ifetch": ifetch, "handoff": handoff, "scratch": scratch}
+    for name in OPT_IN:
+        fake = globals()[f"Fake{name.capitalize()}Lib"](n=n, physical=physical, **(given[name] or {}))
+        importlib.import_module(f"..ops.{name}", __package__).lib = lambda fake=fake: fake

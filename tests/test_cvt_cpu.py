@@ -894,5 +894,5 @@ def test_the_build_has_a_cvt_target():
     t = B._targets()
     assert "cvt" in t and t["cvt"]["out"].endswith("libmi355x_cvt.so")
     assert t["cvt"]["cmd"] == t["xgmi"]["cmd"] and t["cvt"]["headers"][0].endswith("cvt_ref.h")
-    assert [os.path.basename(h) for h in t["cvt"]["headers"]] == ["cvt_ref.h", "hip_host.h", "simd_report.h"]
+    assert [os.path.basename(h) for h in t["cvt"]["headers"]] == ["cvt_ref.h", "hip_host.h", "simd_report.h", "op_list.h"]
     assert "libmi355x_cvt.so" in B.__doc__ and "vmem,cvt" in B.__doc__

@@ -563,11 +563,12 @@ def test_the_build_has_an_ifetch_target():
     t = B._targets()
     assert "ifetch" in t and t["ifetch"]["out"].endswith("libmi355x_ifetch.so")
     assert t["ifetch"]["cmd"] == t["xgmi"]["cmd"] and t["ifetch"]["headers"][0].endswith("ifetch_ref.h")
-    assert [os.path.basename(h) for h in t["ifetch"]["headers"][1:]] == ["hip_host.h", "simd_report.h"]
+    assert [os.path.basename(h) for h in t["ifetch"]["headers"][1:]] == ["hip_host.h", "simd_report.h", "op_list.h"]
     assert "libmi355x_ifetch.so" in B.__doc__
     with open(os.path.join(CSRC, "ifetch.hip")) as f:
         src = f.read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../common/hip_host.h", "../common/simd_report.h", "ifetch_ref.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["../common/hip_host.h", "../common/op_list.h", "../common/simd_report.h",
+                                                       "ifetch_ref.h"]
     out = t["ifetch"]["out"]
     if not os.path.exists(out):
         pytest.skip("the library is not built")

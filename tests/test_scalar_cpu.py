@@ -647,7 +647,7 @@ def test_the_build_has_a_scalar_target(tmp_path, monkeypatch):
     t = B._targets()
     assert "scalar" in t and t["scalar"]["out"].endswith("libmi355x_scalar.so")
     assert t["scalar"]["cmd"] == t["lanes"]["cmd"]
-    assert [os.path.basename(h) for h in t["scalar"]["headers"]] == ["scalar_ref.h", "hip_host.h", "simd_report.h"]
+    assert [os.path.basename(h) for h in t["scalar"]["headers"]] == ["scalar_ref.h", "hip_host.h", "simd_report.h", "op_list.h"]
     assert "libmi355x_scalar.so" in B.__doc__ and "scalar" in B.__doc__.splitlines()[2]
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
